@@ -15,9 +15,20 @@ frame is split, so scaling is "strong".  value = rays traced by all ranks
 (torch.distributed.run, before anything touches a GPU); a world size that
 differs from --gpus is an error.
 
-Rank 0 prints ONE JSON line with a roofline object for the trace kernel and
-a cpu_baseline measured with the C oracle (single-thread brute force, the
-reference's algorithm) on a bounded pixel sample of the same frame.
+A plain run sets up, warms up, times the K steps and rank 0 prints ONE JSON
+line (value, ms_per_step and what the timed steps themselves gave).
+`--dump-outputs DIR` also writes what the last timed step rendered
+(DIR/frame.npy, DIR/ray_counts.npy; see dump_outputs): same arguments, same
+inputs, so two builds can be compared output for output.
+
+    python bench.py --full [...]
+
+adds everything that takes runs of its own, outside the timed steps: the
+counting launch behind the roofline object of the trace kernel and the
+canonical counts, the fetch-count build, lone frames, a moving camera,
+rt_render end to end, and a cpu_baseline measured with the C oracle
+(single-thread brute force, the reference's algorithm) on a bounded pixel
+sample of the same frame (`--no-cpu-baseline` leaves that one out).
 """
 import argparse
 import collections
@@ -347,6 +358,30 @@ def cpu_baseline(rt, fr, budget_s, ctx):
     }
 
 
+DUMP_MAX_BYTES = 48 << 20  # a larger frame is dumped as seeded random pixels of at most this size, indices included
+
+
+def dump_outputs(path, frame, st):
+    """--dump-outputs: the frame of the last timed step (a device tensor, rows
+    x columns x channels) as <path>/frame.npy in float32, and the timed steps'
+    ray counters (primary, shadow, reflection) as <path>/ray_counts.npy in
+    float64.  A frame of more than DUMP_MAX_BYTES (the 4K configs) is written
+    as a fixed sample: frame.npy holds the sampled pixels (n x channels) and
+    frame_pixels.npy their row-major pixel indices (float64), the same for
+    every run."""
+    os.makedirs(path, exist_ok=True)
+    img = frame.detach().cpu().numpy().astype(np.float32, copy=False)
+    npix = img.shape[0] * img.shape[1]
+    if img.nbytes > DUMP_MAX_BYTES:
+        n = DUMP_MAX_BYTES // (4 * img.shape[2] + 8)
+        idx = np.sort(np.random.default_rng(20250101).choice(npix, n, replace=False))
+        img = img.reshape(npix, img.shape[2])[idx]
+        np.save(os.path.join(path, "frame_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "frame.npy"), np.ascontiguousarray(img))
+    np.save(os.path.join(path, "ray_counts.npy"),
+            np.array([st.primary_rays, st.shadow_rays, st.reflection_rays], dtype=np.float64))
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -426,7 +461,17 @@ def main():
                     help="N = 1: also time this many frames of an orbiting camera (0 = skip)")
     ap.add_argument("--launch-check", action="store_true",
                     help="test hook: form the process group, report rank/world on stderr, exit (no GPU work)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the counting "
+                         "launch (roofline, canonical counts), lone frames, the moving camera, rt_render end to "
+                         "end, the fetch-count build and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the frame the last timed step rendered (DIR/frame.npy, "
+                         "float32 rows x columns x channels) and the timed steps' summed ray counters "
+                         "(DIR/ray_counts.npy, float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not args.in_process:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -565,6 +610,7 @@ def main():
                               flags=mode_flags | rt.abi.RT_FLAG_ASYNC)
     frame_no = [0]
     last_frame = [0]
+    last_buf = [0]  # the buffer (index into outs) the last enqueued frame renders into
     cam_s, plane_s = rt.raytracing.camera_struct(fr.camera), rt.raytracing.plane_struct(fr.plane)
 
     def close_group(g, used):
@@ -630,6 +676,7 @@ def main():
     def step(cam=None):
         if batch > 1:
             last_frame[0] = frame_no[0]
+            last_buf[0] = frame_no[0] % nbuf
             batch_cams.append(cam or cam_s)
             frame_no[0] += 1
             if len(batch_cams) == G:
@@ -642,6 +689,7 @@ def main():
             b = pick_stream()  # (one output buffer per stream: nbuf == nstreams here)
         sb = streams[(j if dist_on else b) % nstreams]
         last_frame[0] = f
+        last_buf[0] = b
         ctx.set_stream(sb.cuda_stream)
         if dist_on:
             if j == 0:  # the group's previous gather: done and reassembled, buffers free
@@ -683,14 +731,16 @@ def main():
                     finish_gather(g)
         ctx.set_stream(stream.cuda_stream)
 
-    # counting launch (untimed): algorithmic work of this rank's frame, and
-    # the camera samples the Scene.AABB gate rejects before any object test
-    cparams = rt.frame_params(fr, band_index=params.band_index, band_count=band_count, band_rows=R,
-                              flags=rt.abi.RT_FLAG_COUNT_TESTS | mode_flags)
-    cst = ctx.render_device(fr.camera, fr.plane, cparams, out.data_ptr(), nbytes)
-    logical = logical_bytes(cst, rx, local_rows)
-    canonical = canonical_check(fr.name, cst, band_count == 1)
-    scene_misses = int(cst.primary_scene_misses)
+    # counting launch (untimed, --full): algorithmic work of this rank's frame,
+    # and the camera samples the Scene.AABB gate rejects before any object test
+    logical, canonical, scene_misses = None, None, 0
+    if args.full:
+        cparams = rt.frame_params(fr, band_index=params.band_index, band_count=band_count, band_rows=R,
+                                  flags=rt.abi.RT_FLAG_COUNT_TESTS | mode_flags)
+        cst = ctx.render_device(fr.camera, fr.plane, cparams, out.data_ptr(), nbytes)
+        logical = logical_bytes(cst, rx, local_rows)
+        canonical = canonical_check(fr.name, cst, band_count == 1)
+        scene_misses = int(cst.primary_scene_misses)
 
     # setup, untimed: one frame on each stream before the W warmup steps.  A
     # stream's first frame allocates its longest-first state in the library
@@ -736,18 +786,26 @@ def main():
     kernel_ms = st.kernel_ms
     timed_launch = ctx.last_launch()  # the instance and split shape the last timed frame ran (RT_DEBUG_LAST_LAUNCH)
     sky_tiles = int(timed_launch.split("sky=")[1].split()[0]) if "sky=" in timed_launch else 0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left for its caller: the frame (rank 0's
+        # reassembled image when the rows are sharded) and rank 0's counters
+        # summed over the timed steps
+        lb = last_buf[0]
+        dump_outputs(args.dump_outputs, images[lb // G][lb % G, :ry] if dist_on else outs[lb], st)
     # a lone frame's kernel time (the same frames back to back on one stream,
     # no gather): such frames split their slowest tiles, so this is the split
     # instance — what one synchronous Update() frame costs
-    for _ in range(args.steps):
-        ctx.render_device(fr.camera, fr.plane, aparams, out.data_ptr(), nbytes)
-    lone_kernel_ms = ctx.finish().kernel_ms
-    lone_launch = ctx.last_launch()
+    lone_kernel_ms, lone_launch = 0.0, None
+    if args.full:
+        for _ in range(args.steps):
+            ctx.render_device(fr.camera, fr.plane, aparams, out.data_ptr(), nbytes)
+        lone_kernel_ms = ctx.finish().kernel_ms
+        lone_launch = ctx.last_launch()
 
     # a moving camera (N = 1): every frame from another viewpoint, so the
     # longest-first order always comes from earlier, different frames
     moving = None
-    if not dist_on and not args.sim_bands and args.moving_frames > 0:
+    if args.full and not dist_on and not args.sim_bands and args.moving_frames > 0:
         cams = orbit_cameras(rt, fr.camera, args.moving_frames)
         for c in cams[:8]:  # warm the orbit's first views
             step(c)
@@ -771,7 +829,7 @@ def main():
     e2e_ms = None
     e2e8_ms = None
     d2h_ms = None
-    if not dist_on and not args.sim_bands and rank == 0:
+    if args.full and not dist_on and not args.sim_bands and rank == 0:
         host = np.empty((ry, rx, 4), dtype=np.float32)
         host8 = np.empty((ry, rx, 4), dtype=np.uint8)
         ctx.set_stream(stream.cuda_stream)
@@ -847,7 +905,7 @@ def main():
             pmc, pmc_state = None, f"not measured for batch launches ({batch} frames a launch)"
         rays_per_frame = rays // args.steps
         fetched = fetched_leg(args.config, avg_kernel_s, rt, fr,
-                              band_count == 1 and batch == 1 and args.mode == "megakernel")
+                              band_count == 1 and batch == 1 and args.mode == "megakernel") if args.full else {}
         line = {
             "metric": METRIC,
             "value": rays / elapsed / 1e6,
@@ -902,7 +960,8 @@ def main():
                 # rank 0's host time per enqueued frame: near ms_per_step means host-bound
                 "host_enqueue_ms_per_frame": host_s / args.steps * 1e3,
             },
-            "roofline": {**roofline(pmc, pmc_state, kname, avg_kernel_s, logical), "canonical_counts": canonical,
+            "roofline": None if not args.full else {
+                         **roofline(pmc, pmc_state, kname, avg_kernel_s, logical), "canonical_counts": canonical,
                          # the requested (cache-level) bytes: per-wave packet fetches, per-lane chain fetches
                          "fetched_bytes_per_launch": fetched.get("bytes_per_launch"), "fetched": fetched,
                          # whole frames in flight: the order's sky tail in a second launch per frame
@@ -911,7 +970,15 @@ def main():
                              f"sky_batch_kernel<{'true' if fr.spp == 4 else 'false'}>",
                              "with_tiles": sky_tiles} if sky_tiles else {})},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.full:
+            # a plain run reports what its timed steps gave; the figures that take
+            # runs of their own (--full) are left out, not reported as zero
+            del line["roofline"]
+            for k in ("rays_trivial_miss", "rays_in_scene", "mrays_per_s_in_scene", "lone_launch",
+                      "lone_kernel_ms_per_frame", "lone_kernel", "end_to_end_ms_per_frame",
+                      "end_to_end_rgba8_ms_per_frame", "d2h_copy_ms_per_frame", "moving_camera"):
+                del line["config"][k]
+        elif world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(rt, fr, args.cpu_seconds, ctx)
         print(json.dumps(line), flush=True)
     ctx.close()
@@ -942,7 +1009,7 @@ def main_in_process(args):
     cam_s, plane_s = rt.raytracing.camera_struct(fr.camera), rt.raytracing.plane_struct(fr.plane)
     aparams = rt.frame_params(fr, flags=rt.abi.RT_FLAG_ASYNC)
     cparams = rt.frame_params(fr, flags=rt.abi.RT_FLAG_COUNT_TESTS)
-    cst = ctx.render_device(cam_s, plane_s, cparams, outs[0].data_ptr(), nbytes)
+    cst = ctx.render_device(cam_s, plane_s, cparams, outs[0].data_ptr(), nbytes) if args.full else None
     frame = [0]
 
     def step():
@@ -963,6 +1030,8 @@ def main_in_process(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     rays = st.primary_rays + st.shadow_rays + st.reflection_rays
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[(frame[0] - 1) % len(streams)], st)
     verified = None
     if args.verify:
         single = rt.Context()
@@ -997,7 +1066,7 @@ def main_in_process(args):
             "parallelism": f"in-process row-bands x{info['num_devices']} on devices {info['devices']} + "
                            + {0: "no gather", 1: "peer-copy gather", 2: "RCCL gather"}[info["gather"]],
             "rays_per_frame": rays // args.steps,
-            "rays_trivial_miss": int(cst.primary_scene_misses),
+            **({"rays_trivial_miss": int(cst.primary_scene_misses)} if cst is not None else {}),
             "frames_in_flight": len(streams),
             "kernel_ms_per_frame": st.kernel_ms / args.steps,
             "host_enqueue_ms_per_frame": host_s / args.steps * 1e3,

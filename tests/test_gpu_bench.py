@@ -1,5 +1,6 @@
 """bench.py end to end on the GPU (subprocesses, as the driver runs it): the
-single-GPU line's schema, and the distributed frame loop — grouped RCCL
+single-GPU line's schema (`--full`), a plain run with `--dump-outputs`
+against a frame rendered here, and the distributed frame loop — grouped RCCL
 gathers of row shards, partial groups, one reassembly launch per group —
 at one rank over RCCL and at two ranks over gloo, each checked with
 `--verify` (the reassembled frame must equal a single-rank frame bit for
@@ -44,7 +45,7 @@ def _verified(stderr):
 
 
 def test_bench_single_gpu_line():
-    p = _run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"])
+    p = _run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"])
     d = _metric_line(p.stdout)
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "Mrays/s"
     assert d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
@@ -54,6 +55,35 @@ def test_bench_single_gpu_line():
     assert c["resolution"] == "1920x1080" and c["spp"] == 4 and c["depth"] == 8
     assert c["rays_per_frame"] > 1920 * 1080 * 4  # primary + shadow + mirror rays
     assert c["end_to_end_ms_per_frame"] > c["kernel_ms_per_frame"] > 0
+
+
+def test_bench_plain_run_dumps_its_last_frame(tmp_path, rt):
+    """A plain run (no --full) prints the headline line without the figures
+    that take runs of their own, and --dump-outputs writes the last timed
+    step's frame: the C3 frame, bit for bit what rt_render_device gives."""
+    import numpy as np
+    import torch
+
+    p = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs",
+              str(tmp_path / "dump")])
+    d = _metric_line(p.stdout)
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True
+    assert "roofline" not in d and "cpu_baseline" not in d and "moving_camera" not in d["config"]
+    assert sorted(os.listdir(tmp_path / "dump")) == ["frame.npy", "ray_counts.npy"]
+    frame = np.load(tmp_path / "dump" / "frame.npy")
+    counts = np.load(tmp_path / "dump" / "ray_counts.npy")
+    assert frame.dtype == np.float32 and frame.shape == (1080, 1920, 4)
+    assert counts.dtype == np.float64 and counts.sum() == d["config"]["rays_per_frame"] * 3
+    fr = rt.make("C3")
+    ctx = rt.Context()
+    try:
+        ctx.set_scene(fr.scene)
+        ref = torch.empty((1080, 1920, 4), dtype=torch.float32, device="cuda")
+        ctx.render_device(fr.camera, fr.plane, rt.frame_params(fr), ref.data_ptr(), ref.numel() * 4)
+        assert np.array_equal(frame.view(np.int32), ref.cpu().numpy().view(np.int32))
+    finally:
+        ctx.close()
 
 
 def test_bench_rccl_path_one_rank_partial_groups():

@@ -9,7 +9,7 @@ out=gpurun_out/sched_${TAG}.jsonl
 line() {  # variant config rep
   local v=$1 c=$2 r=$3 lib=""
   [ "$v" != default ] && lib="--lib $v"
-  timeout -k 10 200 python bench.py --config $c --steps ${STEPS:-200} --warmup 5 --no-cpu-baseline --moving-frames 0 $lib \
+  timeout -k 10 200 python bench.py --config $c --steps ${STEPS:-200} --warmup 5 --full --no-cpu-baseline --moving-frames 0 $lib \
     > gpurun_out/sched_${v}_${c}_$r.log 2>&1 || { echo "FAIL $v $c $r"; tail -n 20 gpurun_out/sched_${v}_${c}_$r.log; exit 1; }
   grep '^{' gpurun_out/sched_${v}_${c}_$r.log | tail -n 1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({'v':'$v','cfg':'$c','r':$r,'value':round(d['value']),'ms':round(d['ms_per_step'],5),'kms':round(d['config']['kernel_ms_per_frame'],5),'lone':round(d['config']['lone_kernel_ms_per_frame'],5),'canon':d['roofline'].get('canonical_counts')}))" | tee -a $out
 }

@@ -11,7 +11,7 @@ out=gpurun_out/skylone_${TAG}.jsonl
 line() {  # variant config rep
   local v=$1 c=$2 r=$3 lib="" log=gpurun_out/skylone_${1}_${2}_${3}.log
   [ "$v" != default ] && lib="--lib $v"
-  timeout -k 10 200 python bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline --moving-frames 0 $lib > $log 2>&1 \
+  timeout -k 10 200 python bench.py --config $c --steps 20 --warmup 5 --full --no-cpu-baseline --moving-frames 0 $lib > $log 2>&1 \
     || { echo "FAIL $v $c $r"; tail -n 20 $log; exit 1; }
   grep '^{' $log | tail -n 1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); c=d['config']; print(json.dumps({'v':'$v','cfg':'$c','r':$r,'value':round(d['value']),'lone':round(c['lone_kernel_ms_per_frame'],5),'lone_launch':c['lone_launch'],'e2e8':round(c.get('end_to_end_rgba8_ms_per_frame') or 0,4),'e2e':round(c.get('end_to_end_ms_per_frame') or 0,4)}))" | tee -a $out
 }

@@ -60,7 +60,7 @@ if has smoke; then
   tail -1 $out/smoke_$tag.log
 fi
 if has bench; then
-  timeout -k 10 300 python bench.py > $out/bench_$tag.log 2>&1 || fail bench $out/bench_$tag.log
+  timeout -k 10 300 python bench.py --full > $out/bench_$tag.log 2>&1 || fail bench $out/bench_$tag.log
   tail -1 $out/bench_$tag.log
 fi
 if has drv; then
@@ -156,7 +156,7 @@ if has lines; then
     for i in "${!sets[@]}"; do
       a="${sets[$i]}"
       f=$out/lines_${tag}_${i}_$r.log
-      timeout -k 10 300 python bench.py --no-cpu-baseline --moving-frames 0 $a > $f 2>&1 || fail lines-$i $f
+      timeout -k 10 300 python bench.py --full --no-cpu-baseline --moving-frames 0 $a > $f 2>&1 || fail lines-$i $f
       grep '^{' $f | tail -1 | LARGS="$a" R=$r python3 -c "import sys, json, os; d = json.loads(sys.stdin.read()); \
 c = d['config']; print(json.dumps({'args': os.environ['LARGS'], 'round': int(os.environ['R']), 'mrays': round(d['value'], 1), \
 'ms_per_step': round(d['ms_per_step'], 5), 'kernel_ms': round(c['kernel_ms_per_frame'], 5), \
@@ -167,11 +167,11 @@ c = d['config']; print(json.dumps({'args': os.environ['LARGS'], 'round': int(os.
 fi
 if has cfg; then
   for c in C2 C4 C5; do
-    timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline --moving-frames 0 \
+    timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 1 --full --no-cpu-baseline --moving-frames 0 \
       > $out/bench_${c}_$tag.log 2>&1 || fail bench-$c $out/bench_${c}_$tag.log
   done
   for c in C4 C5; do
-    timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline --moving-frames 0 --sim-bands 8 \
+    timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 1 --full --no-cpu-baseline --moving-frames 0 --sim-bands 8 \
       > $out/sb8_${c}_$tag.log 2>&1 || fail sb8-$c $out/sb8_${c}_$tag.log
   done
   echo cfg-ok

@@ -3,8 +3,8 @@
     python tools/window_timeline.py gpurun_out/ktw_<tag> --steps 20
 
 The timed frames are the last --steps dispatches of the in-flight render
-instance (bench.py --moving-frames 0: the lone frames after the window run
-another instance) and the sky / tally kernels between the first of them and
+instance (bench.py --full --moving-frames 0: the lone frames after the window
+run another instance) and the sky / tally kernels between the first of them and
 the window's last render end.  Prints one JSON line: the window's device span
 (first timed start -> last timed kernel end) against K x the steady per-frame
 period (the median start-to-start spacing of the timed renders), and how the
