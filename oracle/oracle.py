@@ -71,6 +71,7 @@ def lib():
         L.orc_bvh4_free.argtypes = [P]
         L.orc_bvh4_free.restype = None
         L.orc_render_pixels_bvh4.argtypes = [P, P, P, P, P, P, C.c_int32, P, P, C.c_int32]
+        L.orc_render_pixels_bvh4_stack.argtypes = [P, P, P, P, P, P, C.c_int32, P, P, P, C.c_int32]
         _lib = L
     return _lib
 
@@ -210,12 +211,15 @@ class Bvh4Scene:
         idx = np.ascontiguousarray(pixel_indices, np.int32)
         out = np.zeros((len(idx), 4), np.float32)
         cnt = orc_counts()
-        st = lib().orc_render_pixels_bvh4(self.h, C.cast(self.desc.ref(), C.c_void_p), C.byref(cam), C.byref(pl),
-                                          C.byref(prm), _p(idx), len(idx), _p(out), C.byref(cnt),
-                                          threads or default_threads())
+        high = (C.c_uint64 * 3)()
+        st = lib().orc_render_pixels_bvh4_stack(self.h, C.cast(self.desc.ref(), C.c_void_p), C.byref(cam),
+                                                C.byref(pl), C.byref(prm), _p(idx), len(idx), _p(out), C.byref(cnt),
+                                                high, threads or default_threads())
         if st != 0:
             raise RuntimeError(f"oracle render failed: {st}")
-        return out, cnt.as_dict()
+        # the most entries the walk's stack held at once, per ray class
+        return out, dict(cnt.as_dict(), stack_high_camera=high[0], stack_high_reflection=high[1],
+                         stack_high_shadow=high[2])
 
     def close(self):
         if self.h:

@@ -211,6 +211,17 @@ typedef struct orc_counts {
     uint64_t box_tests, triangle_tests, sphere_tests, shading_fetches;
 } orc_counts;
 
+/* Inside the renderer the counts carry, for the 4-wide walk only, the most
+ * stack entries any camera / reflection / shadow ray of the pixels held at
+ * once, i.e. what the per-lane GPU traversal of the same tree (traverse.h)
+ * needs.  orc_counts, the callers' struct, keeps its seven fields;
+ * orc_render_pixels_bvh4_stack hands the high-waters out beside it. */
+enum { RAY_CAMERA = 0, RAY_REFLECTION = 1, RAY_SHADOW = 2 };
+typedef struct {
+    orc_counts c;
+    uint64_t stack_high[3]; /* by ray class */
+} pix_counts;
+
 /* ------------------------------------------------------------------------
  * Optional CPU BVH for the closest-hit query (CPU-baseline only: separates
  * the algorithmic speed-up of a BVH from the GPU's).  Same answer as the
@@ -480,7 +491,8 @@ void orc_bvh4_free(void *h) {
 /* One query.  any: shadow ray, true when some primitive has t*t < d2 (node
  * culling at tlimit); otherwise the closest hit (best, best_rank). */
 static int bvh4_query(const orc_bvh4 *B, const rt_scene_desc *sc, const rt_aabb *scene_box, const rt_ray *ray,
-                      int any, float tlimit, float d2, float *best_out, int *rank_out, orc_tests *ct) {
+                      int any, float tlimit, float d2, float *best_out, int *rank_out, orc_tests *ct,
+                      uint64_t *stack_high) {
     *best_out = FLT_MAX;
     *rank_out = -1;
     ct->box++;
@@ -521,6 +533,7 @@ static int bvh4_query(const orc_bvh4 *B, const rt_scene_desc *sc, const rt_aabb 
             if (key[0] == INFINITY) goto pop;
             const int nh = 1 + (key[1] != INFINITY) + (key[2] != INFINITY) + (key[3] != INFINITY);
             for (int k = nh - 1; k >= 1; --k) stack[sp++] = ch[k];
+            if (stack_high && (uint64_t)sp > *stack_high) *stack_high = (uint64_t)sp;
             ref = ch[0];
             continue;
         } else {
@@ -587,13 +600,13 @@ static int bvh4_query(const orc_bvh4 *B, const rt_scene_desc *sc, const rt_aabb 
 }
 
 static rt_hit bvh4_intersect(const orc_bvh4 *B, const rt_scene_desc *sc, const rt_aabb *scene_box,
-                             const rt_ray *ray, orc_tests *ct) {
+                             const rt_ray *ray, orc_tests *ct, uint64_t *stack_high) {
     rt_hit hit;
     hit.type = 0; hit.index = -1; hit.mesh_index = -1;
     hit.distance = FLT_MAX;
     float best;
     int r;
-    if (!bvh4_query(B, sc, scene_box, ray, 0, 0.0f, 0.0f, &best, &r, ct)) return hit;
+    if (!bvh4_query(B, sc, scene_box, ray, 0, 0.0f, 0.0f, &best, &r, ct, stack_high)) return hit;
     hit.distance = best;
     if (r < B->mt) {
         const int m = B->mesh_of[r];
@@ -615,8 +628,8 @@ typedef struct {
     const orc_bvh4 *bvh4; /* non-null: the GPU's tree (closest hits; shadow rays any-hit) */
 } frame_t;
 
-static rt_hit trace(const frame_t *fr, const rt_ray *ray, orc_tests *ct) {
-    if (fr->bvh4) return bvh4_intersect(fr->bvh4, fr->sc, &fr->scene_box, ray, ct);
+static rt_hit trace(const frame_t *fr, const rt_ray *ray, orc_tests *ct, uint64_t *stack_high) {
+    if (fr->bvh4) return bvh4_intersect(fr->bvh4, fr->sc, &fr->scene_box, ray, ct, stack_high);
     return fr->bvh ? bvh_intersect(fr->bvh, fr->sc, &fr->scene_box, ray, ct)
                    : intersect(fr->sc, &fr->scene_box, ray, ct);
 }
@@ -632,12 +645,16 @@ static f3 calc_specular(f3 light_dir, f3 ray_dir, f3 n, f3 ks, f3 irr, float pho
     return mul(muls(ks, upow(c, phong)), irr);
 }
 
+static void add_tests(pix_counts *cnt, const orc_tests *ct) {
+    cnt->c.box_tests += ct->box; cnt->c.triangle_tests += ct->tri; cnt->c.sphere_tests += ct->sph;
+}
+
 /* RayTracingSetup.Shade, :304-366 (literal recursion) */
-static f3 shade(const frame_t *fr, rt_ray ray, int bounce, orc_counts *cnt) {
+static f3 shade(const frame_t *fr, rt_ray ray, int bounce, pix_counts *cnt) {
     orc_tests ct = {0, 0, 0};
-    rt_hit hit = trace(fr, &ray, &ct);
+    rt_hit hit = trace(fr, &ray, &ct, &cnt->stack_high[bounce ? RAY_REFLECTION : RAY_CAMERA]);
     if (hit.type == 0) {
-        cnt->box_tests += ct.box; cnt->triangle_tests += ct.tri; cnt->sphere_tests += ct.sph;
+        add_tests(cnt, &ct);
         return fr->bg255;
     }
     const rt_scene_desc *sc = fr->sc;
@@ -657,7 +674,7 @@ static f3 shade(const frame_t *fr, rt_ray ray, int bounce, orc_counts *cnt) {
         n = sc->mesh_triangle_normals[mesh->first_triangle + hit.index];
         mat = &mesh->material;
     }
-    cnt->shading_fetches++;
+    cnt->c.shading_fetches++;
     /* CalculateAmbient :438-441: ambientRadiance * ambientReflectance */
     f3 color = mul(sc->ambient_radiance, mat->ambient_reflectance);
     f3 ray_dir = normalize(sub(ray.origin, p));
@@ -667,16 +684,16 @@ static f3 shade(const frame_t *fr, rt_ray ray, int bounce, orc_counts *cnt) {
         rt_ray shadow;
         shadow.origin = add(p, muls(n, SHADOW_RAY_EPSILON));
         shadow.direction = light_dir;
-        cnt->shadow_rays++;
+        cnt->c.shadow_rays++;
         float light_dist_sq = distancesq(p, pl->position);
         if (fr->bvh4) { /* any-hit on the GPU's tree: the same predicate (t >= 0, so t*t is monotone) */
             float bt;
             int br;
             if (bvh4_query(fr->bvh4, sc, &fr->scene_box, &shadow, 1, sqrtf(light_dist_sq) * 1.001f, light_dist_sq, &bt,
-                           &br, &ct))
+                           &br, &ct, &cnt->stack_high[RAY_SHADOW]))
                 continue;
         } else {
-            rt_hit sh = trace(fr, &shadow, &ct);
+            rt_hit sh = trace(fr, &shadow, &ct, NULL);
             if (sh.type != 0) {
                 float hd2 = sh.distance * sh.distance;
                 if (hd2 < light_dist_sq) continue;
@@ -690,13 +707,13 @@ static f3 shade(const frame_t *fr, rt_ray ray, int bounce, orc_counts *cnt) {
                                     mat->phong_exponent);
         color = add(color, add(diffuse, specular));
     }
-    cnt->box_tests += ct.box; cnt->triangle_tests += ct.tri; cnt->sphere_tests += ct.sph;
+    add_tests(cnt, &ct);
     if (mat->is_mirror && bounce < fr->max_bounces) {
         /* Reflect :368-373: origin P + N*eps, dir (2*N)*dot(V,N) - V (not renormalised) */
         rt_ray refl;
         refl.origin = add(p, muls(n, SHADOW_RAY_EPSILON));
         refl.direction = sub(muls(smul(2.0f, n), dot(ray_dir, n)), ray_dir);
-        cnt->reflection_rays++;
+        cnt->c.reflection_rays++;
         f3 sub_color = shade(fr, refl, bounce + 1, cnt);
         color = add(color, mul(mat->mirror_reflectance, sub_color));
     }
@@ -713,7 +730,7 @@ static int isqrt_exact(int v) {
 /* One pixel: CastPixelRays :288-300 with the n*n stratified extension
  * (n == 1 reproduces the reference's fixed 0.5 offsets bit for bit). */
 static void pixel(const frame_t *fr, const rt_camera *cam, f3 top_left, float hl, float vl,
-                  int res_x, int res_y, int n, int x, int y, float *out4, orc_counts *cnt) {
+                  int res_x, int res_y, int n, int x, int y, float *out4, pix_counts *cnt) {
     f3 sum = V(0, 0, 0);
     for (int sj = 0; sj < n; ++sj) {
         float oy = ((float)sj + 0.5f) / (float)n;
@@ -725,7 +742,7 @@ static void pixel(const frame_t *fr, const rt_camera *cam, f3 top_left, float hl
             rt_ray ray;
             ray.origin = cam->position;
             ray.direction = normalize(sub(pix, cam->position));
-            cnt->primary_rays++;
+            cnt->c.primary_rays++;
             f3 c = shade(fr, ray, 0, cnt);
             sum = (sj == 0 && si == 0) ? c : add(sum, c);
         }
@@ -765,31 +782,41 @@ static f3 top_left_of(const rt_camera *cam, const rt_image_plane *plane) {
 /* Render the pixels listed in pix_idx (x + y*res_x) into out (4 floats each). */
 static int render_pixels(const orc_bvh *bvh, const orc_bvh4 *bvh4, const rt_scene_desc *sc, const rt_camera *cam,
                          const rt_image_plane *plane, const rt_render_params *prm, const int32_t *pix_idx,
-                         int32_t npix, float *out, orc_counts *counts, int32_t threads);
+                         int32_t npix, float *out, orc_counts *counts, uint64_t *stack_high, int32_t threads);
 
 int orc_render_pixels(const rt_scene_desc *sc, const rt_camera *cam, const rt_image_plane *plane,
                       const rt_render_params *prm, const int32_t *pix_idx, int32_t npix,
                       float *out, orc_counts *counts, int32_t threads) {
-    return render_pixels(NULL, NULL, sc, cam, plane, prm, pix_idx, npix, out, counts, threads);
+    return render_pixels(NULL, NULL, sc, cam, plane, prm, pix_idx, npix, out, counts, NULL, threads);
 }
 
 /* The same pixels through the GPU's own 4-wide BVH (orc_bvh4_create). */
 int orc_render_pixels_bvh4(const void *bvh4, const rt_scene_desc *sc, const rt_camera *cam,
                            const rt_image_plane *plane, const rt_render_params *prm, const int32_t *pix_idx,
                            int32_t npix, float *out, orc_counts *counts, int32_t threads) {
-    return render_pixels(NULL, (const orc_bvh4 *)bvh4, sc, cam, plane, prm, pix_idx, npix, out, counts, threads);
+    return render_pixels(NULL, (const orc_bvh4 *)bvh4, sc, cam, plane, prm, pix_idx, npix, out, counts, NULL, threads);
+}
+
+/* The same, and stack_high[3]: the most entries the walk's stack held at once
+ * over the pixels' camera, reflection and shadow rays. */
+int orc_render_pixels_bvh4_stack(const void *bvh4, const rt_scene_desc *sc, const rt_camera *cam,
+                                 const rt_image_plane *plane, const rt_render_params *prm, const int32_t *pix_idx,
+                                 int32_t npix, float *out, orc_counts *counts, uint64_t *stack_high,
+                                 int32_t threads) {
+    return render_pixels(NULL, (const orc_bvh4 *)bvh4, sc, cam, plane, prm, pix_idx, npix, out, counts, stack_high,
+                         threads);
 }
 
 /* The same pixels with closest hits through a CPU BVH (orc_bvh_build over sc). */
 int orc_render_pixels_bvh(const void *bvh, const rt_scene_desc *sc, const rt_camera *cam,
                           const rt_image_plane *plane, const rt_render_params *prm, const int32_t *pix_idx,
                           int32_t npix, float *out, orc_counts *counts, int32_t threads) {
-    return render_pixels((const orc_bvh *)bvh, NULL, sc, cam, plane, prm, pix_idx, npix, out, counts, threads);
+    return render_pixels((const orc_bvh *)bvh, NULL, sc, cam, plane, prm, pix_idx, npix, out, counts, NULL, threads);
 }
 
 static int render_pixels(const orc_bvh *bvh, const orc_bvh4 *bvh4, const rt_scene_desc *sc, const rt_camera *cam,
                          const rt_image_plane *plane, const rt_render_params *prm, const int32_t *pix_idx,
-                         int32_t npix, float *out, orc_counts *counts, int32_t threads) {
+                         int32_t npix, float *out, orc_counts *counts, uint64_t *stack_high, int32_t threads) {
     frame_t fr;
     int n;
     int st = setup(&fr, sc, plane, prm, &n);
@@ -800,22 +827,28 @@ static int render_pixels(const orc_bvh *bvh, const orc_bvh4 *bvh4, const rt_scen
     float hl = plane->half_horizontal_length * 2.0f; /* HorizontalLength, ImagePlane.cs:23 */
     float vl = plane->half_vertical_length * 2.0f;
     int res_x = plane->resolution_x, res_y = plane->resolution_y;
-    uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0;
+    uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0, h0 = 0, h1 = 0, h2 = 0;
     if (threads < 1) threads = 1;
 #pragma omp parallel for schedule(dynamic, 16) num_threads(threads) \
-    reduction(+ : c0, c1, c2, c3, c4, c5, c6)
+    reduction(+ : c0, c1, c2, c3, c4, c5, c6) reduction(max : h0, h1, h2)
     for (int32_t k = 0; k < npix; ++k) {
-        orc_counts cnt;
+        pix_counts cnt;
         memset(&cnt, 0, sizeof cnt);
         int32_t idx = pix_idx[k];
         pixel(&fr, cam, tl, hl, vl, res_x, res_y, n, idx % res_x, idx / res_x, out + 4 * (size_t)k, &cnt);
-        c0 += cnt.primary_rays; c1 += cnt.shadow_rays; c2 += cnt.reflection_rays;
-        c3 += cnt.box_tests; c4 += cnt.triangle_tests; c5 += cnt.sphere_tests; c6 += cnt.shading_fetches;
+        c0 += cnt.c.primary_rays; c1 += cnt.c.shadow_rays; c2 += cnt.c.reflection_rays;
+        c3 += cnt.c.box_tests; c4 += cnt.c.triangle_tests; c5 += cnt.c.sphere_tests; c6 += cnt.c.shading_fetches;
+        if (cnt.stack_high[RAY_CAMERA] > h0) h0 = cnt.stack_high[RAY_CAMERA];
+        if (cnt.stack_high[RAY_REFLECTION] > h1) h1 = cnt.stack_high[RAY_REFLECTION];
+        if (cnt.stack_high[RAY_SHADOW] > h2) h2 = cnt.stack_high[RAY_SHADOW];
     }
     if (counts) {
         counts->primary_rays = c0; counts->shadow_rays = c1; counts->reflection_rays = c2;
         counts->box_tests = c3; counts->triangle_tests = c4; counts->sphere_tests = c5;
         counts->shading_fetches = c6;
+    }
+    if (stack_high) {
+        stack_high[0] = h0; stack_high[1] = h1; stack_high[2] = h2;
     }
     return RT_OK;
 }

@@ -11,6 +11,7 @@ row slabs, and the device-built trees."""
 import numpy as np
 import pytest
 
+from lbvh_scenes import translated as _translated
 from test_gpu_fuzz import random_frame
 
 pytestmark = pytest.mark.gpu
@@ -26,28 +27,6 @@ def _render(ctx, rt, fr, build=0, cut=True, **kw):
 
 def _same(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
-def _translated(rt, fr, off):
-    """The frame with every position moved by `off` (float32 adds, the camera
-    too): the same picture far from the origin."""
-    import copy
-
-    o = np.asarray(off, np.float32)
-    sc = copy.deepcopy(fr.scene)
-    td = sc.TriangleData
-    if len(td.Triangles):
-        td.Triangles = (td.Triangles + o).astype(np.float32)
-    for m in sc.Meshes:
-        m.Triangles = (m.Triangles + o).astype(np.float32)
-        m.AABB = (m.AABB + o).astype(np.float32)
-    if len(sc.SphereData.Spheres):
-        sc.SphereData.Spheres[:, :3] = (sc.SphereData.Spheres[:, :3] + o).astype(np.float32)
-    if len(sc.PointLights):
-        sc.PointLights[:, :3] = (sc.PointLights[:, :3] + o).astype(np.float32)
-    cam = fr.camera.__class__(**{**fr.camera.__dict__,
-                                 "Position": tuple((np.asarray(fr.camera.Position, np.float32) + o).tolist())})
-    return fr.with_(scene=sc, camera=cam)
 
 
 CASES = [("C3", (96, 54), 4), ("C3", (61, 37), 1), ("C2", (80, 45), 4), ("C5", (48, 27), 4), ("demo", None, 1),

@@ -7,6 +7,8 @@ bit-identical to the host-SAH build."""
 import numpy as np
 import pytest
 
+from lbvh_scenes import degenerate_scenes
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
@@ -117,41 +119,8 @@ def test_dynamic_rebuild_per_frame(gpu_ctx, rt, orc):
 def test_degenerate_scenes(gpu_ctx, rt, orc, build):
     """Morton-code collisions (identical centroids), a single primitive, a
     one-triangle mesh, zero-area triangles, a huge-coordinate scene."""
-    S = rt.Scene
     fr0 = rt.make("C1").with_resolution(40, 30)
-    mats = fr0.scene.SphereData.Materials
-    scenes = []
-    # 300 identical spheres plus 200 identical triangles: every key collides
-    a = S()
-    for i in range(300):
-        a.add_sphere_r2((0.1, -0.2, 0.3), 0.2, mats[i % 2])
-    tri = np.array([[[-0.5, -0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.5, 0.5]]], np.float32)
-    a.add_triangles(np.repeat(tri, 200, 0), [mats[1]] * 200)
-    scenes.append(a)
-    # single sphere; single loose triangle; one mesh with one triangle
-    b = S()
-    b.add_sphere_r2((0.0, 0.0, 0.0), 0.25, mats[1])
-    scenes.append(b)
-    c = S()
-    c.add_triangles(tri, [mats[1]])
-    scenes.append(c)
-    d = S()
-    d.add_mesh(rt.Mesh.from_vertices(tri.reshape(-1, 3), [0, 1, 2], mats[1]))
-    scenes.append(d)
-    # zero-area triangles among normal ones
-    e = S()
-    z = np.array([[[0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]],
-                  [[-0.3, 0.0, 0.2], [0.3, 0.0, 0.2], [0.6, 0.0, 0.2]]], np.float32)
-    e.add_triangles(np.concatenate([z, tri]), [mats[0]] * 3)
-    scenes.append(e)
-    # big coordinates: a far plane of spheres
-    f = S()
-    for i in range(64):
-        f.add_sphere_r2((1.0e4 * (i % 8 - 3.5), 1.0e4 * (i // 8 - 3.5), 5.0e4), 1.0e7, mats[i % 2])
-    scenes.append(f)
-    for i, sc in enumerate(scenes):
-        sc.PointLights = fr0.scene.PointLights
-        sc.AmbientLight = fr0.scene.AmbientLight
+    for i, sc in enumerate(degenerate_scenes(rt, fr0)):
         fr = fr0.with_(scene=sc)
         img, st = _frame(gpu_ctx, rt, fr, build)
         ref, counts = orc.render(fr)

@@ -4,7 +4,10 @@
 // structural invariants the kernels rely on are checked: every primitive lands
 // in exactly one leaf, leaves are homogeneous in (kind, mesh gate), child boxes
 // contain their primitives' padded bounds, BVH2 depth <= kMaxTreeDepth, and the
-// 4-wide refs stay in range.  Exit status 0 = all invariants hold.
+// 4-wide refs stay in range, reach every primitive exactly once, and the
+// 4-wide depth fits the traversal stack (3 * (depth4 + 1) <= kStackTotal).
+// Exit status 0 = all invariants hold.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -54,35 +57,89 @@ void walk2(const rtb::BuildResult &B, const std::vector<rtb::Prim> &P, int ref, 
     walk2(B, P, N.d.y, depth + 1, c);
 }
 
-// Every primitive's padded box lies inside each 4-wide node box on its path.
-void walk4(const std::vector<rtd::BvhNode4> &N4, const std::vector<rtb::Prim> &P, const rtb::BuildResult &B,
-           int node, const float lo[3], const float hi[3], int depth, int &leaves) {
+// The primitives of a case, found again by (kind, payload) after build_bvh
+// has reordered the array.
+struct ByPayload {
+    std::vector<const rtb::Prim *> tri, sph;
+};
+
+struct Box3 {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    void grow(const float *l, const float *h) {
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = std::fmin(lo[a], l[a]);
+            hi[a] = std::fmax(hi[a], h[a]);
+        }
+    }
+};
+
+// Every primitive's padded box lies inside each 4-wide child box on its path:
+// each used slot's box must contain the union of the padded boxes of the
+// primitives below it (collected per leaf through tri_order / sph_order), and
+// that union is handed up, so a box anywhere on a primitive's path that does
+// not contain it fails.  Counts how often each primitive is reached through
+// the 4-wide tree; d4 = the deepest node (root 0).
+Box3 walk4(const std::vector<rtd::BvhNode4> &N4, const ByPayload &P, const rtb::BuildResult &B, int node, int depth,
+           int &leaves, int &d4, Counts &c) {
+    Box3 all;
     CHECK(node >= 0 && node < (int)N4.size(), "node4 %d", node);
-    if (node < 0 || node >= (int)N4.size() || depth > 64) return;
+    if (node < 0 || node >= (int)N4.size() || depth > 64) return all;
+    d4 = std::max(d4, depth);
     const rtd::BvhNode4 &n = N4[(size_t)node];
     const float *lx = &n.lox.x, *hx = &n.hix.x, *ly = &n.loy.x, *hy = &n.hiy.x, *lz = &n.loz.x, *hz = &n.hiz.x;
     const int *ch = &n.child.x;
     for (int k = 0; k < 4; ++k) {
-        if (std::isinf(lx[k]) && lx[k] > 0) continue;  // an unused slot
         const float clo[3] = {lx[k], ly[k], lz[k]}, chi[3] = {hx[k], hy[k], hz[k]};
+        if (std::isinf(lx[k]) && lx[k] > 0) {  // an unused slot: +inf on every face, the sentinel leaf
+            for (int a = 0; a < 3; ++a)
+                CHECK(std::isinf(clo[a]) && clo[a] > 0 && std::isinf(chi[a]) && chi[a] > 0, "node4 %d slot %d", node, k);
+            CHECK(ch[k] == rtd::encode_leaf((int)B.tri_order.size(), 1, rtd::kLeafTri), "node4 %d slot %d: empty ref %d",
+                  node, k, ch[k]);
+            continue;
+        }
         for (int a = 0; a < 3; ++a) CHECK(clo[a] <= chi[a], "inverted child box");
-        (void)lo;
-        (void)hi;
+        Box3 sub;
         if (ch[k] >= 0) {
-            walk4(N4, P, B, ch[k], clo, chi, depth + 1, leaves);
+            CHECK(ch[k] != 0, "node4 %d slot %d points at the root", node, k);
+            sub = walk4(N4, P, B, ch[k], depth + 1, leaves, d4, c);
         } else {
             ++leaves;
+            const int v = ~ch[k], first = v & ((1 << 27) - 1), count = ((v >> 27) & 3) + 1, kind = (v >> 29) & 1;
+            const std::vector<int> &order = kind == rtd::kLeafTri ? B.tri_order : B.sph_order;
+            const std::vector<const rtb::Prim *> &src = kind == rtd::kLeafTri ? P.tri : P.sph;
+            std::vector<int> &seen = kind == rtd::kLeafTri ? c.seen_tri : c.seen_sph;
+            CHECK(first + count <= (int)order.size(), "node4 %d slot %d: leaf %d+%d of %zu", node, k, first, count,
+                  order.size());
+            for (int i = first; i < first + count && i < (int)order.size(); ++i) {
+                const int pay = order[(size_t)i];
+                CHECK(pay >= 0 && pay < (int)src.size(), "payload %d", pay);
+                if (pay < 0 || pay >= (int)src.size()) continue;
+                seen[(size_t)pay]++;
+                const rtb::Prim &p = *src[(size_t)pay];
+                CHECK(p.kind == kind && p.gate == src[(size_t)order[(size_t)first]]->gate,
+                      "node4 %d slot %d: leaf mixes kinds or gates", node, k);
+                sub.grow(p.lo, p.hi);
+            }
         }
+        for (int a = 0; a < 3; ++a)
+            CHECK(clo[a] <= sub.lo[a] && sub.hi[a] <= chi[a],
+                  "node4 %d slot %d axis %d: box [%g, %g] does not contain its primitives' padded bounds [%g, %g]", node,
+                  k, a, clo[a], chi[a], sub.lo[a], sub.hi[a]);
+        all.grow(sub.lo, sub.hi);
     }
+    return all;
 }
 
-int run_case(const char *name, std::vector<rtb::Prim> P) {
+int run_case(const char *name, std::vector<rtb::Prim> P, bool expect_forced = false) {
     const int before = g_fail;
     const int n = (int)P.size();
     int ntri = 0, nsph = 0;
     for (const auto &p : P) (p.kind == rtd::kLeafTri ? ntri : nsph)++;
+    int depth4 = 0;
     rtb::BuildResult B = rtb::build_bvh(P, 4);
     CHECK(B.max_depth <= rtd::kMaxTreeDepth, "%s: depth %d", name, B.max_depth);
+    // the case meant to drive the builder into its forced-median mode does so
+    CHECK((B.forced_splits > 0) == expect_forced, "%s: %d forced splits", name, B.forced_splits);
     Counts c;
     c.seen_tri.assign((size_t)ntri, 0);
     c.seen_sph.assign((size_t)nsph, 0);
@@ -97,14 +154,25 @@ int run_case(const char *name, std::vector<rtb::Prim> P) {
         }
         std::vector<rtd::BvhNode4> N4;
         const int d4 = rtb::collapse_bvh4(B, N4, rtd::encode_leaf(ntri, 1, rtd::kLeafTri));
-        CHECK(d4 >= 0 && d4 * 3 <= rtd::kStackTotal, "%s: bvh4 depth %d", name, d4);
-        int leaves = 0;
-        const float inf[3] = {INFINITY, INFINITY, INFINITY};
-        if (!N4.empty()) walk4(N4, P, B, 0, inf, inf, 0, leaves);
+        // the traversal stack: three entries per 4-wide level, the root's included (rt_scene.cpp)
+        CHECK(d4 >= 0 && 3 * (d4 + 1) <= rtd::kStackTotal, "%s: bvh4 depth %d", name, d4);
+        ByPayload by;
+        by.tri.assign((size_t)ntri, nullptr);
+        by.sph.assign((size_t)nsph, nullptr);
+        for (const auto &p : P) (p.kind == rtd::kLeafTri ? by.tri : by.sph)[(size_t)p.payload] = &p;
+        Counts c4;
+        c4.seen_tri.assign((size_t)ntri, 0);
+        c4.seen_sph.assign((size_t)nsph, 0);
+        int leaves = 0, walked = 0;
+        if (!N4.empty()) walk4(N4, by, B, 0, 0, leaves, walked, c4);
         CHECK(leaves >= 1, "%s: no leaves in bvh4", name);
+        CHECK(walked == d4, "%s: bvh4 depth %d reported, %d walked", name, d4, walked);
+        for (int i = 0; i < ntri; ++i) CHECK(c4.seen_tri[(size_t)i] == 1, "%s: bvh4 tri %d seen %d", name, i, c4.seen_tri[(size_t)i]);
+        for (int i = 0; i < nsph; ++i) CHECK(c4.seen_sph[(size_t)i] == 1, "%s: bvh4 sph %d seen %d", name, i, c4.seen_sph[(size_t)i]);
+        depth4 = d4;
     }
-    std::printf("%-28s prims %7d nodes %7zu leaves %7zu depth %2d %s\n", name, n, B.nodes.size(), B.leaves.size(),
-                B.max_depth, g_fail == before ? "ok" : "FAIL");
+    std::printf("%-28s prims %7d nodes %7zu leaves %7zu depth %2d depth4 %2d forced %5d %s\n", name, n,
+                B.nodes.size(), B.leaves.size(), B.max_depth, depth4, B.forced_splits, g_fail == before ? "ok" : "FAIL");
     return g_fail - before;
 }
 
@@ -117,6 +185,58 @@ rtb::Prim prim(float x, float y, float z, float r, int kind, int gate, int paylo
     p.gate = gate;
     p.payload = payload;
     return p;
+}
+
+// The loose deep-chain scene of scenes.py deep_chain(levels), restated as
+// Prims: clusters of `per` identical triangle boxes in the sibling half-cells
+// of the Morton path (10 bits per axis, x first) towards P inside [-1, 1]^3,
+// half-extents 4 * 2^(-L/3) cut to stay centred and inside the box, the
+// builders' padding, and the two tiny triangles that pin the scene box.  Big
+// siblings around a shrinking chain: the binned-SAH splits meet the geometry
+// that makes the device builder's tree one level deep per key bit.
+std::vector<rtb::Prim> deep_chain_prims(int levels, int per) {
+    const double P[3] = {0.2371, -0.1513, 0.3127};
+    const float pad_abs = 0x1p-13f;  // scene scale 1
+    std::vector<rtb::Prim> out;
+    int payload = 0;
+    auto add = [&](const double c[3], const double h[3]) {
+        rtb::Prim p;
+        float ext = 0.0f;
+        for (int a = 0; a < 3; ++a) {
+            p.lo[a] = (float)(c[a] - h[a]);
+            p.hi[a] = (float)(c[a] + h[a]);
+            ext = std::max(ext, p.hi[a] - p.lo[a]);
+        }
+        const float pad = pad_abs + ext * 1e-4f;
+        for (int a = 0; a < 3; ++a) {
+            p.c[a] = 0.5f * (p.lo[a] + p.hi[a]);
+            p.lo[a] -= pad;
+            p.hi[a] += pad;
+        }
+        p.kind = rtd::kLeafTri;
+        p.gate = -1;
+        p.payload = payload++;
+        out.push_back(p);
+    };
+    const double tiny[3] = {5e-4, 5e-4, 0.0};
+    const double pin_lo[3] = {-1.0 + 5e-4, -1.0 + 5e-4, -1.0}, pin_hi[3] = {1.0 - 5e-4, 1.0 - 5e-4, 1.0};
+    add(pin_lo, tiny);
+    add(pin_hi, tiny);
+    int q[3];
+    for (int a = 0; a < 3; ++a) q[a] = std::min(1023, (int)((P[a] + 1.0) / 2.0 * 1024.0));
+    for (int L = 0; L < levels; ++L) {
+        const int axis = L % 3, j = L / 3;
+        double c[3], h[3];
+        for (int b = 0; b < 3; ++b) {
+            const int nb = b <= axis ? j + 1 : j;
+            int pre = nb ? q[b] >> (10 - nb) : 0;
+            if (b == axis) pre ^= 1;
+            c[b] = -1.0 + (pre + 0.5) * 2.0 / (double)(1 << nb);
+            h[b] = std::min(2.0 * std::pow(2.0, -L / 3.0) * 2.0, 0.98 * std::min(c[b] + 1.0, 1.0 - c[b]));
+        }
+        for (int i = 0; i < per; ++i) add(c, h);
+    }
+    return out;
 }
 
 }  // namespace
@@ -140,7 +260,7 @@ int main() {
     {
         std::vector<rtb::Prim> P;  // a collinear chain that would exceed depth 31 without forced medians
         for (int i = 0; i < 70000; ++i) P.push_back(prim(std::ldexp(1.0f, i % 100 - 50), 0, 0, 0.0f, rtd::kLeafTri, -1, i));
-        run_case("exponential chain x70000", P);
+        run_case("exponential chain x70000", P, true);
     }
     {
         std::vector<rtb::Prim> P;  // mixed kinds and 50 mesh gates
@@ -153,6 +273,12 @@ int main() {
         }
         run_case("mixed kinds/gates x20000", P);
     }
+    // The SAH answers big siblings around a shrinking chain with splits balanced in
+    // area x count (2-wide depth 11 and 7 here), so these sets stay far from
+    // kMaxTreeDepth and never enter the forced-median mode; that mode needs
+    // depth + log2(n) >= 31, which only the zero-extent exponential chain above reaches.
+    run_case("deep chain 30 x16", deep_chain_prims(30, 16));
+    run_case("deep chain 30 x1", deep_chain_prims(30, 1));
     for (int s = 0; s < 20; ++s) {
         std::vector<rtb::Prim> P;
         const int n = 1 + (int)(rng() % 3000);

@@ -97,6 +97,7 @@ struct Builder {
         if (n == 1) return make_leaf(begin, end);
 
         const bool forced = depth + ceil_log2(n) >= rtd::kMaxTreeDepth;
+        if (forced) ++R.forced_splits;
         int best_axis = -1, best_split = -1;
         float best_cost = std::numeric_limits<float>::infinity();
         if (!forced) {

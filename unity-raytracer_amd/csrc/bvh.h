@@ -34,6 +34,7 @@ struct BuildResult {
     std::vector<int> tri_order;  // payloads of triangle leaves, leaf order
     std::vector<int> sph_order;  // payloads of sphere leaves, leaf order
     int max_depth = 0;
+    int forced_splits = 0;  // nodes split at the median because the depth bound left no room for SAH
     double build_ms = 0.0;
 };
 

@@ -298,6 +298,106 @@ def mirror_corridor(depth=40, res=(24, 12), spp=1, loose=True) -> Frame:
                  background=(0.1, 0.2, 0.3, 1.0), max_bounces=depth, spp=spp)
 
 
+def _morton_chain(lo, hi, point, levels, bits):
+    """Clusters along the Morton path of `point` inside the box [lo, hi]
+    (`bits` bits per axis, x first): for key bit L the centre of the sibling
+    half-cell — the cell that shares L bits with the point's code and differs
+    in bit L — and a half-extent per axis of about 4 * 2^(-L/3) of the box's,
+    cut so the cluster stays centred and inside the box.  -> [(centre, half)]"""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    cells = 1 << bits
+    q = np.minimum(((np.asarray(point, np.float64) - lo) / (hi - lo) * cells).astype(np.int64), cells - 1)
+    out = []
+    for L in range(levels):
+        a, j = L % 3, L // 3
+        c = np.zeros(3)
+        for b in range(3):
+            nb = j + 1 if b <= a else j                     # bits of axis b fixed at this level
+            pre = int(q[b]) >> (bits - nb) if nb else 0
+            if b == a:
+                pre ^= 1                                    # the sibling half
+            c[b] = lo[b] + (pre + 0.5) * (hi[b] - lo[b]) / (1 << nb)
+        half = np.minimum(2.0 * 2.0 ** (-L / 3.0) * (hi - lo), 0.98 * np.minimum(c - lo, hi - c))
+        out.append((c, half))
+    return out
+
+
+def _cluster_tris(c, h, count):
+    """`count` copies of one triangle whose bounding box is c -+ h exactly
+    (every axis attains both faces), so its centroid key is c's."""
+    t = np.array([c + h * (-1, -1, -1), c + h * (1, 1, -1), c + h * (-1, 1, 1)], np.float64)
+    return np.repeat(t[None], count, 0).astype(f32)
+
+
+def deep_chain(levels=30, variant="loose", per=16, res=(48, 27), spp=1, bounces=2, camera_offset=(0.0, 0.0, 0.0),
+               origin=(0.0, 0.0, 0.0)) -> Frame:
+    """A scene whose device-built tree (csrc/lbvh.hip) is as deep as the
+    sort key is long: clusters of `per` identical primitives sit in the
+    sibling half-cells of a Morton path towards an interior point P, their
+    extents shrinking by 2^(-1/3) per key bit, so at every Karras level the
+    sibling cluster's surface area exceeds that of the rest of the chain, the
+    4-wide collapse spends both its expansions on the cluster, and the chain
+    costs one 4-wide level per key bit.  Two tiny triangles pin the scene box
+    to [-1, 1]^3; the camera sits at P (+ camera_offset) inside most cluster
+    boxes; one light is inside the chain and one outside the box; one cluster
+    is a mirror.  With 16 per cluster a cluster and its halves stay internal
+    nodes (quarters of 4 become leaves).
+
+    variant "loose": loose triangles, one cluster per key bit (levels <= 30).
+    variant "spheres": every third cluster is made of spheres.
+    variant "mesh": min(levels, 30) one-cluster meshes whose centres form the
+    30-bit top chain, and an innermost mesh around P that continues the chain
+    in its in-mesh key bits for the remaining levels.
+    origin: the whole scene translated (float32 adds)."""
+    P = np.array([0.2371, -0.1513, 0.3127])
+    lo, hi = np.full(3, -1.0), np.full(3, 1.0)
+    sc = Scene()
+    mats = [MIRROR if L == 5 else (BOX_MAT, KNOT_MAT, BLUE_PLASTIC)[L % 3] for L in range(64)]
+    tiny = 1e-3 * np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]])
+    pins = np.stack([lo + tiny, hi - tiny]).astype(f32)
+    top = min(levels, 30)
+    chain = _morton_chain(lo, hi, P, top, 10)
+    loose, loose_mats = [pins], [WHITE, WHITE]
+    for L, (c, h) in enumerate(chain):
+        if variant == "mesh":
+            t = _cluster_tris(c, h, per)
+            sc.add_mesh(_mesh_from_tris(t, None, mats[L]))
+        elif variant == "spheres" and L % 3 == 1:
+            rad = min(float(h.min()), 0.6 * float(np.linalg.norm(c - P)))  # the camera stays outside
+            for _ in range(per):
+                sc.add_sphere_r2(c, rad * rad, mats[L])
+        else:
+            loose.append(_cluster_tris(c, h, per))
+            loose_mats += [mats[L]] * per
+    if variant == "mesh":
+        # the innermost mesh: its box is centred on P's cell, pinned by two tiny
+        # triangles of its own; its clusters follow the path of a point inside it
+        r = 0.003  # smaller than the last top-level cluster, so the rule above holds across the seam
+        ilo, ihi = P - r, P + r
+        inner = [np.stack([ilo + r * tiny, ihi - r * tiny]).astype(f32)]
+        for c, h in _morton_chain(ilo, ihi, P + r * np.array([0.137, -0.211, 0.093]), levels - top, 9):
+            inner.append(_cluster_tris(c, h, per))
+        sc.add_mesh(_mesh_from_tris(np.concatenate(inner), None, KNOT_MAT))
+    sc.add_triangles(np.concatenate(loose), loose_mats)
+    sc.add_point_light(tuple(P + (0.02, 0.01, 0.03)), 8.0)
+    sc.add_point_light((3.0, 3.5, -3.0), 900.0)
+    sc.AmbientLight = np.array(AMBIENT, f32)
+    cam = CameraData(Position=tuple((P + np.asarray(camera_offset)).astype(f32).tolist()))
+    fr = Frame(f"deep_chain_{variant}{levels}", sc, cam, ImagePlane(res[0], res[1], 1.0, 0.8889, 0.5),
+               background=(0.1, 0.2, 0.3, 1.0), max_bounces=bounces, spp=spp)
+    o = np.asarray(origin, f32)
+    if o.any():
+        td = sc.TriangleData
+        td.Triangles = (td.Triangles + o).astype(f32)
+        for m in sc.Meshes:
+            m.Triangles, m.AABB = (m.Triangles + o).astype(f32), (m.AABB + o).astype(f32)
+        if len(sc.SphereData.Spheres):
+            sc.SphereData.Spheres[:, :3] = (sc.SphereData.Spheres[:, :3] + o).astype(f32)
+        sc.PointLights[:, :3] = (sc.PointLights[:, :3] + o).astype(f32)
+        fr = fr.with_(camera=replace(cam, Position=tuple((np.asarray(cam.Position, f32) + o).tolist())))
+    return fr
+
+
 def torus_knot(p=2, q=3, segments=384, sides=90, scale=0.22, tube=0.085, center=(0.0, -0.15, 0.15)):
     """(p,q) torus-knot tube: segments x sides quads = 2*segments*sides tris."""
     phi = np.arange(segments, dtype=np.float64) * (2 * np.pi / segments)
