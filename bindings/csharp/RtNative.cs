@@ -196,6 +196,17 @@ namespace RayTracer.Native
                                                                       int pixelBytes, IntPtr image);
         [DllImport(Lib)] public static extern int rt_intersect_rays(IntPtr ctx, [In] RtRay[] rays, int n,
                                                                    [Out] RtHit[] hits);
+        // Device-resident ray queries: every pointer but ctx / p / stats is device memory on the
+        // context's GPU; enqueued on the context's stream (rt_set_stream), nothing awaited.
+        [DllImport(Lib)] public static extern int rt_intersect_rays_device(IntPtr ctx, IntPtr deviceRays, int n,
+                                                                          IntPtr deviceHits);
+        [DllImport(Lib)] public static extern int rt_occluded_rays_device(IntPtr ctx, IntPtr deviceRays,
+                                                                         IntPtr deviceMaxDistanceSq, int n,
+                                                                         IntPtr deviceOccluded);
+        // stats: IntPtr.Zero (stream-ordered) or a pinned RtStats (the call then waits for the stream)
+        [DllImport(Lib)] public static extern int rt_shade_rays_device(IntPtr ctx, IntPtr deviceRays, int n,
+                                                                      ref RtRenderParams p, IntPtr deviceColors,
+                                                                      UIntPtr outBytes, IntPtr stats);
         [DllImport(Lib)] public static extern float rt_spec_threshold();
         [DllImport(Lib)] public static extern int rt_debug_set(IntPtr ctx, int what, int value);  // tests only
         [DllImport(Lib)] public static extern int rt_debug_read(IntPtr ctx, int what, IntPtr output, long capacityBytes, out long bytesWritten);  // measuring builds only

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 6
+#define RT_ABI_VERSION 7
 
 /* ---- status codes ------------------------------------------------------ */
 typedef enum rt_status {
@@ -440,6 +440,48 @@ int rt_synchronize(rt_ctx *ctx);
 /* Batch closest-hit query: Scene.IntersectRay (Scene.cs:43-122) for n host
  * rays; writes n host rt_hit records. */
 int rt_intersect_rays(rt_ctx *ctx, const rt_ray *rays, int32_t n, rt_hit *out_hits);
+
+/* ---- device-resident ray queries ----------------------------------------
+ * For callers whose rays already lie in HBM (a tensor, the output of their
+ * own kernel).  Common rules of the three calls below:
+ *   - every d_* pointer is DEVICE memory on the context's GPU (a multi-device
+ *     context: device 0, which answers the whole batch);
+ *   - the work is enqueued on the context's stream (rt_set_stream) and the
+ *     call returns without waiting: the caller orders its own work with that
+ *     stream or calls rt_synchronize;
+ *   - no device allocation, no copy of the rays and no host decode per call;
+ *   - n == 0 returns RT_OK and launches nothing; n < 0 or a null required
+ *     pointer is RT_E_INVALID; a call before rt_set_scene is RT_E_STATE;
+ *   - directions are the caller's to normalise (the reference only asserts
+ *     it, RayTracingSetup.cs:306);
+ *   - d_hits and d_out_rgba are written as 16-byte records and must be
+ *     16-byte aligned (RT_E_INVALID otherwise); d_rays needs 4-byte alignment. */
+
+/* Scene.IntersectRay (Scene.cs:43-122) for n device rays -> n device rt_hit
+ * records, the same values rt_intersect_rays returns (miss: type 0, index -1,
+ * mesh_index -1, distance FLT_MAX; the stale MeshIndex of Scene.cs:94-97,
+ * 109-112 included). */
+int rt_intersect_rays_device(rt_ctx *ctx, const rt_ray *d_rays, int32_t n, rt_hit *d_hits);
+
+/* The reference's shadow test (RayTracingSetup.cs:333-345) as a query:
+ * d_occluded[i] = 1 iff IntersectRay(ray i) hits something and
+ * Distance * Distance < d_max_distance_sq[i] (float32 product, strict <),
+ * else 0.  d_max_distance_sq == NULL: 1 iff the ray hits anything.  The walk
+ * stops at the first occluder. */
+int rt_occluded_rays_device(rt_ctx *ctx, const rt_ray *d_rays, const float *d_max_distance_sq,
+                            int32_t n, int32_t *d_occluded);
+
+/* RayTracingSetup.Shade(ray, 0) (:304-366) for n caller-supplied rays:
+ * d_out_rgba[i] is the float RGBA Color (alpha 1) that a camera ray equal to
+ * ray i would have produced.  From params: background_color and
+ * max_reflection_bounces (0..32; more: RT_E_INVALID).  samples_per_pixel
+ * must be 0 or 1 and flags 0 (else RT_E_INVALID); the band fields are
+ * ignored.  out_bytes < n * 16: RT_E_INVALID.
+ * stats == NULL: stream-ordered like the other two.  stats != NULL: the call
+ * waits for the stream and fills primary_rays (= n), shadow_rays,
+ * reflection_rays, shading_fetches, kernel_ms and total_ms (other fields 0). */
+int rt_shade_rays_device(rt_ctx *ctx, const rt_ray *d_rays, int32_t n, const rt_render_params *params,
+                         void *d_out_rgba, size_t out_bytes, rt_stats *stats);
 
 /* Diagnostic: the float threshold T with  d < T  <=>  degrees(acos(d)) > 90f
  * (RayTracingSetup.cs:384-392), which the kernels use instead of acos so the

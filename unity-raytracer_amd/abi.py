@@ -13,9 +13,10 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librt_mi355.so")
 
-RT_ABI_VERSION = 6
-# earlier ABIs an A/B variant may have: version 5 lacks rt_render_device_batch only
-OLDER_ABI_OK = (5,)
+RT_ABI_VERSION = 7
+# earlier ABIs an A/B variant may have: version 6 lacks the device ray queries
+# (rt_*_rays_device), version 5 rt_render_device_batch as well
+OLDER_ABI_OK = (5, 6)
 RT_MAX_BATCH = 8
 
 RT_OK = 0
@@ -238,6 +239,10 @@ SIGNATURES = {
     "rt_synchronize": (C.c_int, [_P]),
     "rt_assemble_bands_ex": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "rt_intersect_rays": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "rt_intersect_rays_device": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "rt_occluded_rays_device": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    "rt_shade_rays_device": (C.c_int, [_P, _P, C.c_int32, C.POINTER(rt_render_params), _P, C.c_size_t,
+                                       C.POINTER(rt_stats)]),
     "rt_debug_set": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "rt_debug_read": (C.c_int, [_P, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
 }

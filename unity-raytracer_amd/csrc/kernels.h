@@ -85,6 +85,22 @@ hipError_t launch_render_wavefront(const rtd::SceneDev &S, const rtd::FrameDev &
 hipError_t launch_intersect(const rtd::SceneDev &S, const float *rays, int n, int4 *out,
                             hipStream_t stream);
 
+// Device-resident ray queries (ray_stream.hip): rays are rt_ray records (6
+// floats) in HBM, one lane per ray; n <= 0 launches nothing.
+// Closest hit with the ObjectId decoded on the device: out[i] = rt_hit {type,
+// index, mesh_index, distance bits}; mesh_count entries (+ 1) in S.mesh_rank_first.
+hipError_t launch_intersect_rays(const rtd::SceneDev &S, const float *rays, int n, int mesh_count, int4 *out,
+                                 hipStream_t stream);
+// The shadow test: out[i] = 1 iff ray i hits with Distance * Distance <
+// limit_sq[i] (null limit_sq: iff it hits at all); stops at the first occluder.
+hipError_t launch_occluded_rays(const rtd::SceneDev &S, const float *rays, const float *limit_sq, int n, int *out,
+                                hipStream_t stream);
+// Shade(ray, 0) per ray: out[i] = Color (float RGBA, alpha 1); max_bounces <=
+// rtd::kMaxBounces; counters (kCounterSlots slots, null: none) receive the
+// primary / shadow / reflection ray and shaded-hit counts.
+hipError_t launch_shade_rays(const rtd::SceneDev &S, const float *rays, int n, int max_bounces, const float bg255[3],
+                             float4 *out, unsigned long long *counters, hipStream_t stream);
+
 // Row-order reassembly of block-cyclic shards gathered back to back.
 hipError_t launch_assemble(const void *gathered, int res_x, int res_y, int band_count, int band_rows,
                            int local_rows, int pixel_bytes, void *image, hipStream_t stream);

@@ -405,6 +405,89 @@ int rt_intersect_rays(rt_ctx *ctx, const rt_ray *rays, int32_t n, rt_hit *out_hi
     return RT_OK;
 }
 
+// ---- device-resident ray queries (ray_stream.hip): enqueued on the context's
+// stream, no allocation, no copy of the rays, no host decode
+
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+int rt_intersect_rays_device(rt_ctx *ctx, const rt_ray *d_rays, int32_t n, rt_hit *d_hits) {
+    if (!ctx) return RT_E_INVALID;
+    if (n < 0 || !d_rays || !d_hits) return fail(ctx, RT_E_INVALID, "rt_intersect_rays_device: bad d_rays/n/d_hits");
+    if (!aligned16(d_hits)) return fail(ctx, RT_E_INVALID, "rt_intersect_rays_device: d_hits is not 16-byte aligned");
+    if (!ctx->has_scene) return fail(ctx, RT_E_STATE, "rt_intersect_rays_device before rt_set_scene");
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    HIP_OR_FAIL(ctx, hipSetDevice(ctx->device));
+    static_assert(sizeof(rt_hit) == sizeof(int4) && sizeof(rt_ray) == 6 * sizeof(float), "ray_stream.hip records");
+    HIP_OR_FAIL(ctx, rtk::launch_intersect_rays(ctx->S, (const float *)d_rays, n, (int)ctx->mesh_rank_first.size() - 1,
+                                                (int4 *)d_hits, ctx->stream));
+    return RT_OK;
+}
+
+int rt_occluded_rays_device(rt_ctx *ctx, const rt_ray *d_rays, const float *d_max_distance_sq, int32_t n,
+                            int32_t *d_occluded) {
+    if (!ctx) return RT_E_INVALID;
+    if (n < 0 || !d_rays || !d_occluded)
+        return fail(ctx, RT_E_INVALID, "rt_occluded_rays_device: bad d_rays/n/d_occluded");
+    if (!ctx->has_scene) return fail(ctx, RT_E_STATE, "rt_occluded_rays_device before rt_set_scene");
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    HIP_OR_FAIL(ctx, hipSetDevice(ctx->device));
+    HIP_OR_FAIL(ctx, rtk::launch_occluded_rays(ctx->S, (const float *)d_rays, d_max_distance_sq, n, d_occluded,
+                                               ctx->stream));
+    return RT_OK;
+}
+
+int rt_shade_rays_device(rt_ctx *ctx, const rt_ray *d_rays, int32_t n, const rt_render_params *params,
+                         void *d_out_rgba, size_t out_bytes, rt_stats *stats) {
+    if (!ctx) return RT_E_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n < 0 || !d_rays || !params || !d_out_rgba)
+        return fail(ctx, RT_E_INVALID, "rt_shade_rays_device: bad d_rays/n/params/d_out_rgba");
+    if (params->max_reflection_bounces < 0 || params->max_reflection_bounces > rtd::kMaxBounces)
+        return fail(ctx, RT_E_INVALID, "rt_shade_rays_device: max_reflection_bounces %d outside [0, %d]",
+                    params->max_reflection_bounces, rtd::kMaxBounces);
+    if (params->samples_per_pixel != 0 && params->samples_per_pixel != 1)
+        return fail(ctx, RT_E_INVALID, "rt_shade_rays_device: one sample per ray (samples_per_pixel %d)",
+                    params->samples_per_pixel);
+    if (params->flags != 0)
+        return fail(ctx, RT_E_INVALID, "rt_shade_rays_device: flags must be 0 (float RGBA output), got %d",
+                    params->flags);
+    if (out_bytes < (size_t)n * sizeof(float4))
+        return fail(ctx, RT_E_INVALID, "output buffer %zu bytes < %zu required", out_bytes, (size_t)n * sizeof(float4));
+    if (!aligned16(d_out_rgba)) return fail(ctx, RT_E_INVALID, "rt_shade_rays_device: d_out_rgba is not 16-byte aligned");
+    if (!ctx->has_scene) return fail(ctx, RT_E_STATE, "rt_shade_rays_device before rt_set_scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    HIP_OR_FAIL(ctx, hipSetDevice(ctx->device));
+    float bg255[3];
+    for (int i = 0; i < 3; ++i) bg255[i] = params->background_color[i] * 255.0f;  // Rgb(Color), Rgb.cs:15-18
+    if (!stats) {
+        HIP_OR_FAIL(ctx, rtk::launch_shade_rays(ctx->S, (const float *)d_rays, n, params->max_reflection_bounces, bg255,
+                                                (float4 *)d_out_rgba, nullptr, ctx->stream));
+        return RT_OK;
+    }
+    // counted: the context's counters, as a synchronous frame takes them
+    // (pending RT_FLAG_ASYNC frames keep theirs: settled first)
+    int st = settle_async(ctx);
+    if (st) return st;
+    HIP_OR_FAIL(ctx, hipMemsetAsync(ctx->d_counters, 0,
+                                    rtd::kCounterSlots * rtd::kCounterWords * sizeof(unsigned long long), ctx->stream));
+    HIP_OR_FAIL(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_OR_FAIL(ctx, rtk::launch_shade_rays(ctx->S, (const float *)d_rays, n, params->max_reflection_bounces, bg255,
+                                            (float4 *)d_out_rgba, ctx->d_counters, ctx->stream));
+    HIP_OR_FAIL(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    unsigned long long counts[rtd::kCounterWords];
+    st = read_counters(ctx, counts);
+    if (st) return st;
+    std::memcpy(ctx->last_counts, counts, sizeof counts);
+    float ms = 0.0f;
+    HIP_OR_FAIL(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    fill_stats(stats, counts, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    return RT_OK;
+}
+
 int rt_debug_set(rt_ctx *ctx, int32_t what, int32_t value) {
     if (!ctx) return RT_E_INVALID;
     if (what == RT_DEBUG_GROUP_SAMPLE_WAVES) {

@@ -174,6 +174,9 @@ struct SceneDev {
     float ambient[3];    // AmbientLight.Radiance
     float spec_threshold;  // d < spec_threshold  <=>  degrees(acos(d)) > 90f
     const CutTable *cut;   // bvh4 scenes: the top-level cut (null: none)
+    // first rank of every mesh, mesh_count + 1 entries (the last: mesh_tri_total):
+    // the device ObjectId decode of the ray queries (ray_stream.hip)
+    const int *mesh_rank_first;
 };
 
 // Longest-first dispatch key of one tile (render_kernel): its shader-clock

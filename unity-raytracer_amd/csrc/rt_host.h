@@ -175,6 +175,7 @@ struct SourceState {
 struct DeviceArrays {
     void *nodes = nullptr, *nodes4 = nullptr, *leaves = nullptr, *tris = nullptr, *sphs = nullptr, *shade = nullptr,
          *mats = nullptr, *lights = nullptr, *gates = nullptr;
+    void *rank_first = nullptr;  // SceneDev::mesh_rank_first
 };
 
 // Frame buffers of a multi-device context for one stream of device 0 (frames
@@ -460,6 +461,8 @@ int run_frame(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, void *
               const BatchIn *bi = nullptr);
 void free_wavefront(rt_ctx *c);
 int settle_async(rt_ctx *ctx);
+// Sums the sharded ray/test counters (waits for the context's stream).
+int read_counters(rt_ctx *ctx, unsigned long long counts[rtd::kCounterWords]);
 void fill_stats(rt_stats *stats, const unsigned long long counts[rtd::kCounterWords], double kernel_ms,
                 double total_ms);
 

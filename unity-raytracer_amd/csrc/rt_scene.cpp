@@ -10,7 +10,8 @@ int warm_up(rt_ctx *ctx);
 
 void free_scene(rt_ctx *c) {
     void **ps[] = {&c->arr.nodes, &c->arr.nodes4, &c->arr.leaves, &c->arr.tris, &c->arr.sphs,
-                   &c->arr.shade, &c->arr.mats,   &c->arr.lights, &c->arr.gates};
+                   &c->arr.shade, &c->arr.mats,   &c->arr.lights, &c->arr.gates,
+                   &c->arr.rank_first};
     for (void **p : ps) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -361,6 +362,8 @@ int set_scene_impl(rt_ctx *ctx, const rt_scene_desc *sc, int32_t build, bool geo
     }
 
     HIP_OR_FAIL(ctx, upload(&ctx->arr.gates, gates));  // before the build: the LBVH keys use the mesh boxes
+    // the device rank decode of the ray queries; ranks do not change under rt_update_mesh_transforms
+    HIP_OR_FAIL(ctx, upload(&ctx->arr.rank_first, ctx->mesh_rank_first));
     rtd::SceneDev &S = ctx->S;
     int nodes_count = 0;
     if ((build == RT_BUILD_LBVH_GPU || build == RT_BUILD_LBVH_GPU_BVH2) && P > 0) {
@@ -488,6 +491,7 @@ int set_scene_impl(rt_ctx *ctx, const rt_scene_desc *sc, int32_t build, bool geo
     S.mats = (const rtd::DevMaterial *)ctx->arr.mats;
     S.lights = (const rtd::DevLight *)ctx->arr.lights;
     S.gates = (const rtd::MeshGate *)ctx->arr.gates;
+    S.mesh_rank_first = (const int *)ctx->arr.rank_first;
     S.num_lights = sc->point_light_count;
     S.mesh_tri_total = MT;
     S.sphere_count = NS;

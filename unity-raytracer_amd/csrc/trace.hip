@@ -815,6 +815,7 @@ __global__ __launch_bounds__(kMkThreads, W) void render_kernel(SceneDev S, Frame
 // flight of one layout, e.g. the frames of one gather group of a rank's row
 // band): whole frames' 6-wave instances, Q4 only; B.f[0] holds the batch's
 // dispatch fields.
+static_assert(sizeof(SceneDev) + sizeof(FrameBatch) <= 4096, "batch kernels: kernel arguments are limited to 4 KB");
 template <bool SPLIT>
 __global__ __launch_bounds__(kMkThreads, kMkMinWaves) void render_batch_kernel(SceneDev S, FrameBatch B) {
     render_wave<false, SPLIT, false, true, kMkMinWaves, false, true>(S, B.f[0], &B);
@@ -865,6 +866,7 @@ struct SkyArgs {
     typename std::conditional<BATCH, FrameBatch, FrameDev>::type P;  // the frame, or the batch (P.f[0]: dispatch)
     int sky_blocks, waves;
 };
+static_assert(sizeof(SkyArgs<true>) <= 4096, "sky_batch_batch_kernel: kernel arguments are limited to 4 KB");
 __device__ __forceinline__ const FrameDev &head(const FrameDev &F) { return F; }
 __device__ __forceinline__ const FrameDev &head(const FrameBatch &B) { return B.f[0]; }
 // The frame of tile t of the argument block's frame or batch (and the tile in

@@ -199,6 +199,37 @@ class RayTracingSetup {
         check(rt_render(ctx_, &c, &p, &prm, reinterpret_cast<float *>(PixelColors.data()), &LastStats));
     }
 
+    // Device-resident ray queries: rays and answers are device memory on the
+    // context's GPU; the work is enqueued on the context's stream and not
+    // awaited (Synchronize(), or the caller's own stream order).
+
+    // Scene.IntersectRay (Scene.cs:43-122) for n device rays -> n device rt_hit records
+    void IntersectRaysDevice(const rt_ray *d_rays, int32_t n, rt_hit *d_hits) {
+        check(rt_intersect_rays_device(ctx_, d_rays, n, d_hits));
+    }
+
+    // The shadow test (:333-345): d_occluded[i] = 1 iff ray i hits with
+    // Distance * Distance < d_max_distance_sq[i] (null: iff it hits anything)
+    void OccludedRaysDevice(const rt_ray *d_rays, const float *d_max_distance_sq, int32_t n, int32_t *d_occluded) {
+        check(rt_occluded_rays_device(ctx_, d_rays, d_max_distance_sq, n, d_occluded));
+    }
+
+    // Shade(ray, 0) (:304-366) per device ray with this setup's BackgroundColor
+    // and MaxReflectionBounces -> n device Colors; stats non-null: waits and fills them
+    void ShadeRaysDevice(const rt_ray *d_rays, int32_t n, Color *d_colors, rt_stats *stats = nullptr) {
+        rt_render_params prm{};
+        prm.background_color[0] = BackgroundColor.r;
+        prm.background_color[1] = BackgroundColor.g;
+        prm.background_color[2] = BackgroundColor.b;
+        prm.background_color[3] = BackgroundColor.a;
+        prm.max_reflection_bounces = MaxReflectionBounces;
+        prm.samples_per_pixel = 1;
+        prm.band_count = 1;
+        check(rt_shade_rays_device(ctx_, d_rays, n, &prm, d_colors, (size_t)std::max(0, n) * sizeof(Color), stats));
+    }
+
+    void Synchronize() { check(rt_synchronize(ctx_)); }
+
     rt_ctx *context() const { return ctx_; }
 
    private:

@@ -267,6 +267,48 @@ class Context:
                                                out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # Device-resident ray queries (rt_*_rays_device): rays, limits and answers
+    # are device memory on the context's GPU, given as integer device pointers
+    # or as objects with data_ptr() (torch tensors).  Enqueued on the context's
+    # stream (set_stream); nothing is awaited unless stats are asked for.
+
+    def intersect_rays_device(self, rays_ptr, n: int, hits_ptr):
+        """Scene.IntersectRay for n device rt_ray records (24 B) -> n device
+        rt_hit records (HIT_DTYPE, 16 B, 16-byte aligned)."""
+        self._check(self.lib.rt_intersect_rays_device(self.h, _dev_ptr(rays_ptr), int(n), _dev_ptr(hits_ptr)))
+
+    def occluded_rays_device(self, rays_ptr, limits_ptr, n: int, out_ptr):
+        """The reference's shadow test per ray: out[i] (int32) = 1 iff ray i
+        hits with Distance * Distance < limits[i] (float32; limits_ptr None:
+        iff it hits anything)."""
+        self._check(self.lib.rt_occluded_rays_device(self.h, _dev_ptr(rays_ptr), _dev_ptr(limits_ptr), int(n),
+                                                     _dev_ptr(out_ptr)))
+
+    def shade_rays_device(self, rays_ptr, n: int, params: abi.rt_render_params, out_ptr, nbytes: int,
+                          want_stats: bool = False):
+        """RayTracingSetup.Shade(ray, 0) per ray: out[i] = float RGBA Color.
+        want_stats: waits for the stream and returns rt_stats (ray counts,
+        device time); otherwise stream-ordered, returns None."""
+        stats = abi.rt_stats() if want_stats else None
+        self._check(self.lib.rt_shade_rays_device(self.h, _dev_ptr(rays_ptr), int(n), C.byref(params),
+                                                  _dev_ptr(out_ptr), C.c_size_t(int(nbytes)),
+                                                  C.byref(stats) if want_stats else None))
+        return stats
+
+    def synchronize(self):
+        """Waits for all work enqueued on the context's stream."""
+        self._check(self.lib.rt_synchronize(self.h))
+
+
+def _dev_ptr(p) -> C.c_void_p:
+    """A device pointer argument: None (null), an integer address or any
+    object with data_ptr()."""
+    if p is None:
+        return C.c_void_p(None)
+    if hasattr(p, "data_ptr"):
+        p = p.data_ptr()
+    return C.c_void_p(int(p))
+
 
 HIT_DTYPE = np.dtype([("type", np.int32), ("index", np.int32), ("mesh_index", np.int32),
                       ("distance", np.float32)])
