@@ -1,7 +1,8 @@
 """Host-side AddressSanitizer + UBSan runs: the BVH builder
 (csrc/bvh.cpp) over random and degenerate primitive sets with its structural
-invariants checked, and the CPU oracle over small scenes with every primitive
-kind and NaN / zero / axis-parallel query rays (tools/asan/)."""
+invariants checked, the CPU oracle over small scenes with every primitive
+kind and NaN / zero / axis-parallel query rays, and a frame's dispatch plan
+(csrc/dispatch_plan.h) over its table and every tile count (tools/asan/)."""
 import os
 import shutil
 import subprocess
@@ -20,7 +21,7 @@ def built():
     return os.path.join(ASAN, "build")
 
 
-@pytest.mark.parametrize("exe", ["bvh_asan", "oracle_asan"])
+@pytest.mark.parametrize("exe", ["bvh_asan", "oracle_asan", "plan_asan"])
 def test_sanitized_driver(built, exe):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
     r = subprocess.run([os.path.join(built, exe)], capture_output=True, text=True, timeout=300, env=env)

@@ -1,6 +1,6 @@
 """Host-side logic that needs no GPU: the longest-first cost key of split
-tiles (rt_device.h tile_cost_key, compiled for the host with hipcc) and
-bench.py's own rank launcher."""
+tiles (rt_device.h tile_cost_key, compiled for the host with hipcc), a
+frame's dispatch plan (dispatch_plan.h) and bench.py's own rank launcher."""
 import json
 import os
 import socket
@@ -47,6 +47,42 @@ int main() {
         assert other == _key(c)  # only part 0 is recorded by the kernel; the key itself is unscaled
         n += 1
     assert n == 20
+
+
+@pytest.fixture(scope="module")
+def plan_driver(tmp_path_factory):
+    """tools/asan/plan_asan.cpp against csrc/dispatch_plan.h, compiled for the host."""
+    exe = tmp_path_factory.mktemp("plan") / "plan"
+    subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-Wall", "-Werror",
+                    "-I", os.path.join(ROOT, "unity-raytracer_amd", "csrc"), "-o", str(exe),
+                    os.path.join(ROOT, "tools", "asan", "plan_asan.cpp")], check=True)
+    return str(exe)
+
+
+def test_dispatch_plan_equals_the_recorded_table(plan_driver):
+    """csrc/dispatch_plan.h plans every input of tests/golden/dispatch_plan.tsv
+    as the table records: splits, sky tail, buffers, waves and the instance
+    name, line for line.  The table was written by the statements that decided
+    a frame's dispatch before the plan existed (rt_frame.cpp lpt_prepare and
+    sky_tail_usable, trace.hip launch_render_mega / launch_render_batch),
+    copied into a program that fed them these inputs."""
+    got = subprocess.run([plan_driver, "table"], capture_output=True, text=True, check=True).stdout.splitlines()
+    want = open(os.path.join(ROOT, "tests", "golden", "dispatch_plan.tsv")).read().splitlines()
+    assert len(want) > 500
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g == w, f"line {k + 1}"
+    assert len(got) == len(want)
+
+
+def test_dispatch_plan_invariants_hold_for_every_tile_count(plan_driver):
+    """Every tile count from 1 to 140,000 at 4 spp under each flag combination
+    and slot state: one-sample waves only with a SAMPLE instance; a sky tail
+    only behind an order, with tallies, leaving the splits and a wave; counting
+    and row-order frames carry no order; levels and deep frames no splits; and
+    plan_dispatch reports no error."""
+    p = subprocess.run([plan_driver, "sweep"], capture_output=True, text=True)
+    assert p.returncode == 0 and "ALL OK" in p.stdout, p.stdout[-3000:] + p.stderr[-2000:]
+    assert " 0 broken" in p.stdout
 
 
 def _free_port():

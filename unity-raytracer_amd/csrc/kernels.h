@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dispatch_plan.h"
 #include "rt_device.h"
 #include "wavefront.h"
 
@@ -17,31 +18,17 @@ constexpr bool kWaveClockBuild = true;
 constexpr bool kWaveClockBuild = false;
 #endif
 
-// Sky tiles per wave at the end of a longest-first order (FrameDev
-// sky_batch_tiles): a tile whose every sample surely misses the scene box is
-// a background store, too little work for a wave of its own (60 % of a C3
-// frame's waves, 12 % of its wave time: wclk_r05s).
-#ifdef RT_EXP_SKYBATCH
-constexpr int kSkyBatch = RT_EXP_SKYBATCH;  // measuring builds only (1: off)
-#else
-constexpr int kSkyBatch = 32;  // C3 in flight: 16 -> 32 +1.2 % / +0.2 % on two boxes, C4 +-0 (r06b, r05w)
-#endif
+using rtp::kSkyBatch;  // sky tiles per wave at the end of a longest-first order (dispatch_plan.h)
 // Count of the tiles before the sorted order's sky tail (cost key 0) into
 // host-mapped memory, one 64-bit store tagged with the sort's sequence number:
 // (seq << 32) | count.
 hipError_t launch_sky_count(const unsigned *cost_sorted, int n, unsigned seq, unsigned long long *out,
                             hipStream_t stream);
 
-// Frames (row shards) of at most this many tiles launch render_kernel's
-// 5-wave instances (trace.hip), the only ones with the one-sample split path.
-constexpr int kShardTilesMax = 70000;
-
 // One frame (or one row shard of it): CastPixelRays + Shade, RayTracingSetup.cs:275-366.
 // Megakernel: one lane per sample, whole Whitted chain in one launch (trace.hip).
 // Longest-first tile order for the next frame (trace.hip).
 size_t tile_sort_scratch_bytes(int n);
-// waves of a render_kernel launch of F (tiles + the extra waves of split tiles)
-int render_mega_waves(const rtd::FrameDev &F);
 // Sums the kCounterSlots sharded counter slots into kCounterWords words at out.
 hipError_t launch_fold_counters(const unsigned long long *counters, unsigned long long *out, hipStream_t stream);
 hipError_t launch_iota(int *p, int n, hipStream_t stream);
@@ -54,20 +41,23 @@ hipError_t launch_build_cut(const rtd::BvhNode4 *nodes, rtd::CutTable *out, hipS
 // the same cut with its boxes re-read from the (refitted) tree
 hipError_t launch_refresh_cut(const rtd::BvhNode4 *nodes, rtd::CutTable *out, hipStream_t stream);
 
+// Launches P.instance (dispatch_plan.h: the plan F's dispatch fields were
+// filled from), then the order's sky tail and the launch's tallies as P says.
 // *instance (nullable): the name of the kernel instance launched (static
 // storage; null when nothing was launched) — rt_debug_read RT_DEBUG_LAST_LAUNCH.
-hipError_t launch_render_mega(const rtd::SceneDev &S, const rtd::FrameDev &F, bool count_tests,
+hipError_t launch_render_mega(const rtd::SceneDev &S, const rtd::FrameDev &F, const rtp::Plan &P,
                               hipStream_t stream, const char **instance = nullptr);
 
 // The frames of a batch (rtd::FrameBatch: whole 4-spp frames of one layout)
 // in one launch: render_batch_kernel, then the batch's sky tail and tallies
 // (sky_batch_batch_kernel) or its tallies alone.
-hipError_t launch_render_batch(const rtd::SceneDev &S, const rtd::FrameBatch &B, hipStream_t stream,
-                               const char **instance = nullptr);
+hipError_t launch_render_batch(const rtd::SceneDev &S, const rtd::FrameBatch &B, const rtp::Plan &P,
+                               hipStream_t stream, const char **instance = nullptr);
 
-// Level-synchronous all-packet megakernel (trace_levels.hip), chosen by
-// launch_render_mega for >= 16 spp on a 4-wide BVH.
-hipError_t launch_render_levels(const rtd::SceneDev &S, const rtd::FrameDev &F, hipStream_t stream);
+// Level-synchronous all-packet megakernel (trace_levels.hip), rtp::kLevels:
+// >= 16 spp on a 4-wide BVH.  *instance (nullable): the instance's name.
+hipError_t launch_render_levels(const rtd::SceneDev &S, const rtd::FrameDev &F, hipStream_t stream,
+                                const char **instance = nullptr);
 
 // Packet megakernel: wave-synchronous levels, coherent rays traced one BVH
 // path per wave (packet.h).

@@ -277,7 +277,7 @@ struct FrameDev {
     // wave's LDS stack area allows (testing knob: a small value makes every
     // step depth-first, rt_debug_set)
     int sample_wave_stack;
-    int in_flight;  // 1: other frames of the context are in flight beside this one (rt_frame.cpp overlapped_frame)
+    int in_flight;  // 1: frames in flight beside this one (dispatch_plan.h Plan::in_flight): no kernel reads it, the host no longer decides from it
     // measuring builds only (RT_EXP_PERSIST): a whole frame's non-split launch
     // as persist_waves resident waves pulling longest-first tiles from eight
     // per-XCD tile counters (persist_ctr, 16 ints apart, zeroed per launch)

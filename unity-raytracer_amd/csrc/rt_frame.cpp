@@ -216,114 +216,6 @@ int prepare_wavefront(rt_ctx *ctx, const rtd::FrameDev &F, int &chunk_tiles, rtw
     return RT_OK;
 }
 
-
-// Quarter-wave splitting of a frame's slowest tiles trades extra work (each
-// quarter re-walks the BVH top) for a shorter critical path; it pays only
-// when the frame (shard) is small enough for its slowest wave to set its
-// time: measured with 3 frames in flight, a 1/8 C3 shard (16,200 tiles)
-// +18 %, a 1/4 shard (32,400) -7 %, a whole frame (129,600) -7 %.  The very
-// slowest of them (1/2048 of the tiles) go further, to sixteen waves of one
-// pixel each: a 1/8 shard's single frame -14 % more, throughput with frames
-// in flight +-1 % (1/512 or more: -5..-15 %).
-#ifdef RT_EXP_SPLIT16DIV
-constexpr int kSplit16Div = RT_EXP_SPLIT16DIV;  // measuring builds only
-#else
-constexpr int kSplit16Div = 2048;  // of those, 1/kSplit16Div of the tiles as sixteenth-waves; 0: off
-#endif
-#ifdef RT_EXP_SPLITDIV
-constexpr int kSplitDiv = RT_EXP_SPLITDIV;  // measuring builds only
-#else
-constexpr int kSplitDiv = 256;  // 1/kSplitDiv of the tiles (the slowest) run as quarter-waves; 0: off
-#endif
-// A lone shard's finely split tiles run as one-sample waves traced by the
-// whole wave (trace.hip render_sample_wave, csrc/coop.h): cheap enough to
-// split its slowest 1/256 so (1/1024 before the whole-wave traversal: the
-// rest of a 1/8 C3 share's slowest waves were whole tiles of ~105 us):
-// single frame -13 % on two 1/8 shares against 1/1024 (r05q).
-#ifdef RT_EXP_SPLIT16SAMPLE
-constexpr int kSplit16DivSample = RT_EXP_SPLIT16SAMPLE;  // measuring builds only
-#else
-constexpr int kSplit16DivSample = 256;
-#endif
-// Larger shards (up to 70,000 tiles: a 1/2 or 1/4 shard of 1080p) split only
-// their slowest 1/4096 into sixteenth-waves: single frame -15..-30 %,
-// throughput with frames in flight +2..4 % on a 1/4 shard; a whole frame
-// (129,600 tiles) loses 2-6 % and does not split.
-#ifdef RT_EXP_SPLITMAX
-constexpr int kSplitMaxTiles = RT_EXP_SPLITMAX;  // measuring builds only
-#else
-constexpr int kSplitMaxTiles = 24000;    // ... in frames/shards of at most this many tiles
-#endif
-#ifdef RT_EXP_SPLIT16MAX
-constexpr int kSplit16MaxTiles = RT_EXP_SPLIT16MAX;  // measuring builds only
-#else
-constexpr int kSplit16MaxTiles = 70000;
-#endif
-constexpr int kSplit16DivLarge = 4096;
-// A lone whole frame (more than kSplit16MaxTiles tiles, no other frame beside
-// it) splits only its slowest 1/16384: C3 single frame -1.7 %, C2 -2.1 %
-// against 1/4096 (1/8192: -1.1 / -1.1 %; r04aq, r04ar); 1/32768 +6 %, one
-// tile +15 % on C3 (r04au).
-#ifdef RT_EXP_SPLIT16WHOLE
-constexpr int kSplit16DivWhole = RT_EXP_SPLIT16WHOLE;  // measuring builds only
-#else
-constexpr int kSplit16DivWhole = 16384;
-#endif
-#ifdef RT_EXP_S64LONE
-constexpr int kSample16LoneTiles = RT_EXP_S64LONE;  // measuring builds only
-#else
-constexpr int kSample16LoneTiles = 40000;  // lone shards up to this many tiles: a sample per wave
-#endif
-// ... and a shard of that size with no other frame beside it (lpt_prepare
-// overlapped_frame: a synchronous Update() frame of one rank) its slowest
-// 1/1024: a 1/2 C3 shard's single frame -10.6 %, frames in flight +-0 (r04n;
-// its slowest waves were whole tiles of ~190 us against a 148-us dispatch).
-// One whose split tiles run as one-sample waves (<= kSample16LoneTiles: a 1/4
-// shard) 1/512 since those trace with the whole wave (its slowest waves were
-// then whole tiles of 120-130 us, wclk_r05p): -12.5 % and +1.4 % on two 1/4
-// shares (r05q).
-#ifdef RT_EXP_SPLIT16LONE
-constexpr int kSplit16DivLone = RT_EXP_SPLIT16LONE;  // measuring builds only
-constexpr int kSplit16DivLoneSample = RT_EXP_SPLIT16LONE;
-#else
-constexpr int kSplit16DivLone = 1024;
-constexpr int kSplit16DivLoneSample = 512;
-#endif
-#ifdef RT_EXP_NOSYNCSPLIT
-constexpr bool kSplitSync = false;  // measuring builds only
-#else
-constexpr bool kSplitSync = true;
-#endif
-// A frame with no other frame beside it (synchronous: Update() waits for it,
-// RayTracingSetup.cs:171-199; or async frames on a single stream) has nothing to
-// hide its tail behind, so whole frames of any size split their slowest 1/4096
-// into sixteenth-waves too: C3 single frame -9 % (0.290 -> 0.264 ms,
-// profiles/r04/abx_split) — a C3 frame's slowest wave, one tile's mirror chains,
-// ran 0.32 ms against 0.24 ms for all the others (tools/wave_clock.py, r04i);
-// frames in flight on several streams keep the 70,000-tile limit.
-// Sky batches only for frames in flight of more than this many tiles: the
-// batch waves run after the frame's render launch, and a small frame in
-// flight is bound by its own latency (a 1/8 C3 share: +32 %; 1/4 −3.1 %, 1/2
-// −1.5 %, whole frames −4.9 % per frame, r06d).
-#ifdef RT_EXP_SKYMIN
-constexpr int kSkyMinTiles = RT_EXP_SKYMIN;  // measuring builds only
-#else
-constexpr int kSkyMinTiles = 24000;
-#endif
-// Lone whole frames take sky batches too (measuring builds: -DRT_EXP_SKYLONE=1)
-#ifdef RT_EXP_SKYLONE
-constexpr bool kSkyLone = RT_EXP_SKYLONE != 0;
-#else
-constexpr bool kSkyLone = false;
-#endif
-#ifdef RT_EXP_LPTPERIOD
-constexpr int kLptPeriod = RT_EXP_LPTPERIOD;  // measuring builds only
-#else
-// frames between longest-first re-sorts (one hipCUB sort ~46 us, plus the
-// measuring launch's clock reads): 32 since round 5 (C3 in flight +1.9 %
-// against 16, 64 +0.4 %: r06p)
-constexpr int kLptPeriod = 32;
-#endif
 // rt_render's host-output pipeline: row slabs alternating over two streams, relative row counts
 // kSlabsCopyBound when the PCIe copy is the longer part (float RGBA: 33 MB at 1080p, 0.59 ms against
 // a 0.29 ms frame — small slabs first so the copy starts early, then slabs the render keeps ahead
@@ -450,101 +342,93 @@ static bool overlapped_frame(const rt_ctx *ctx, const rt_render_params *prm) {
 static bool group_sample_waves(const rt_ctx *ctx) { return !ctx->in_group_frame || ctx->debug_group_sample_waves; }
 
 // Longest-first dispatch of a megakernel launch: picks the state of
-// (stream, slab), points F at the last measured order and decides whether
-// this launch measures costs (the caller sorts them after the launch).
+// (stream, slab), has dispatch_plan.h decide the frame's dispatch from it (P;
+// when P.measure, the caller sorts the measured costs after the launch), and
+// allocates, clears and points F at the buffers P asks for.
 int lpt_prepare(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, bool mega, bool count, int slab,
-                LptSlot *&ls, bool &lpt_sort) {
+                LptSlot *&ls, rtp::Plan &P) {
     ls = nullptr;
-    lpt_sort = false;
     ctx->last_lpt.clear();
     F.tile_order = nullptr;
     F.tile_cost = nullptr;
     F.wave_counts = nullptr;
-    // (a counting launch measures tests, not costs: its per-lane walk is not the
-    // frame a longest-first order is for, and it never answers a tile as sky)
-    if (!mega || count || (prm->flags & RT_FLAG_ROW_ORDER) != 0 || F.num_tiles <= 0) return RT_OK;
-    // a batch launch (rt_render_device_batch): its 6-wave instances split tiles
-    // into quarter- and one-pixel waves, never one-sample waves
-    const bool batch = slab >= kBatchSlab;
-    for (LptSlot &l : ctx->lpt)
-        if (l.used && l.stream == ctx->stream && l.slab == slab) ls = &l;
-    if (!ls)
+    rtp::PlanIn in{};
+    in.num_tiles = F.num_tiles;
+    in.spp = F.spp;
+    in.tile_w = F.tile_w;
+    in.tile_h = F.tile_h;
+    in.max_bounces = F.max_bounces;
+    in.bvh4 = ctx->S.bvh4 != 0;
+    in.count_tests = count;
+    in.row_order = (prm->flags & RT_FLAG_ROW_ORDER) != 0;
+    in.mega = mega;
+    in.overlapped = overlapped_frame(ctx, prm);
+    in.group_sample_waves = group_sample_waves(ctx);
+    in.batch = slab >= kBatchSlab;  // (rt_render_device_batch)
+    long long key = 0;
+    if (rtp::plan_wants_slot(in)) {
         for (LptSlot &l : ctx->lpt)
-            if (!l.used && !ls) {
-                ls = &l;
-                ls->used = true;
-                ls->stream = ctx->stream;
-                ls->slab = slab;
-            }
-    F.in_flight = overlapped_frame(ctx, prm) ? 1 : 0;
-    if (!ls) return RT_OK;  // more (stream, slab) pairs than slots: row-major order
-    const long long key = ((long long)F.num_tiles << 32) ^ ((long long)F.tiles_x << 20) ^ ((long long)F.spp << 12) ^
-                          ((long long)F.band_count << 6) ^ F.band_index ^ ((long long)F.row0 << 44);
-    if (key != ls->key) {
-        const size_t n = (size_t)F.num_tiles;
-        HIP_OR_FAIL(ctx, ensure(ctx, ls->cost, n * 4));
-        HIP_OR_FAIL(ctx, ensure(ctx, ls->cost_sorted, n * 4));
-        HIP_OR_FAIL(ctx, ensure(ctx, ls->order, n * 4));
-        HIP_OR_FAIL(ctx, ensure(ctx, ls->scratch, rtk::tile_sort_scratch_bytes(F.num_tiles)));
-        HIP_OR_FAIL(ctx, ensure(ctx, ls->iota, n * 4));
-        HIP_OR_FAIL(ctx, rtk::launch_iota((int *)ls->iota.p, F.num_tiles, ctx->stream));
-        ls->key = key;
-        ls->valid = false;
-        ls->sky_tail = 0;
-        ls->sky_pending = ls->sky_known = false;  // (a count still in flight is for the old layout)
+            if (l.used && l.stream == ctx->stream && l.slab == slab) ls = &l;
+        if (!ls)
+            for (LptSlot &l : ctx->lpt)
+                if (!l.used && !ls) {
+                    ls = &l;
+                    ls->used = true;
+                    ls->stream = ctx->stream;
+                    ls->slab = slab;
+                }
     }
-    // the sky tail of the last sort, once its count has reached the host (a
-    // plain read of host memory: the count arrives tagged with its sort)
-    if (ls->sky_pending) {
-        const unsigned long long v = *(volatile unsigned long long *)ls->sky_host;
-        if ((unsigned)(v >> 32) == ls->sky_seq) {
-            ls->sky_tail = std::max(0, std::min(F.num_tiles, F.num_tiles - (int)(unsigned)v));
-            ls->sky_pending = false;
+    if (ls) {  // (none: more (stream, slab) pairs than slots, row-major order)
+        key = ((long long)F.num_tiles << 32) ^ ((long long)F.tiles_x << 20) ^ ((long long)F.spp << 12) ^
+              ((long long)F.band_count << 6) ^ F.band_index ^ ((long long)F.row0 << 44);
+        if (key != ls->key) {
+            const size_t n = (size_t)F.num_tiles;
+            HIP_OR_FAIL(ctx, ensure(ctx, ls->cost, n * 4));
+            HIP_OR_FAIL(ctx, ensure(ctx, ls->cost_sorted, n * 4));
+            HIP_OR_FAIL(ctx, ensure(ctx, ls->order, n * 4));
+            HIP_OR_FAIL(ctx, ensure(ctx, ls->scratch, rtk::tile_sort_scratch_bytes(F.num_tiles)));
+            HIP_OR_FAIL(ctx, ensure(ctx, ls->iota, n * 4));
+            HIP_OR_FAIL(ctx, rtk::launch_iota((int *)ls->iota.p, F.num_tiles, ctx->stream));
+            ls->key = key;
+            ls->valid = false;
+            ls->sky_tail = 0;
+            ls->sky_pending = ls->sky_known = false;  // (a count still in flight is for the old layout)
         }
-    }
-    if (ls->scene != ctx->scene_version) {
+        // the sky tail of the last sort, once its count has reached the host (a
+        // plain read of host memory: the count arrives tagged with its sort)
+        if (ls->sky_pending) {
+            const unsigned long long v = *(volatile unsigned long long *)ls->sky_host;
+            if ((unsigned)(v >> 32) == ls->sky_seq) {
+                ls->sky_tail = std::max(0, std::min(F.num_tiles, F.num_tiles - (int)(unsigned)v));
+                ls->sky_pending = false;
+            }
+        }
         // a new or updated scene (rt_update_mesh_transforms every Update): the
         // last order stays a valid permutation of the tiles and, animation being
         // temporally coherent, a good one — keep dispatching by it and keep the
         // re-sort period (re-sorting after every update cost ~55 us a frame)
         ls->scene = ctx->scene_version;
+        if (!ls->valid) ls->frames = 0;
+        in.has_slot = true;
+        in.order_valid = ls->valid;
+        in.frames = ls->frames;
+        in.sky_tail = ls->sky_tail;
     }
-    if (!ls->valid) ls->frames = 0;
-    F.tile_order = ls->valid ? (const int *)ls->order.p : nullptr;
-    // costs are measured and re-sorted every kLptPeriod frames (the sort
-    // costs more than a small frame's tail)
-    lpt_sort = !ls->valid || ls->frames % kLptPeriod == 0;
-    F.tile_cost = lpt_sort ? (unsigned *)ls->cost.p : nullptr;
+    P = rtp::plan_dispatch(in);
+    if (P.error) return fail(ctx, RT_E_INTERNAL, "dispatch plan: invariant %d does not hold", (int)P.error);
+    F.in_flight = P.in_flight ? 1 : 0;
+    F.split_tiles = P.split_tiles;
+    F.split16_tiles = P.split16_tiles;
+    F.s16_shift = P.s16_shift;
+    F.sky_batch_tiles = P.sky_batch_tiles;
+    if (!P.lpt) return RT_OK;
     ++ls->frames;
-    // the most expensive tiles of the last measurement are split into
-    // quarter-waves (a frame's time is bounded below by its slowest wave);
-    // render_kernel only: 16 lanes must hold whole pixels
-    const bool levels = (ctx->S.bvh4 && F.spp >= 16) || F.max_bounces > rtd::kMaxBounces;  // (or deep: no splits)
-    if (F.tile_order && !count && !levels && kSplitDiv > 0 && 16 % F.spp == 0 && F.num_tiles <= kSplitMaxTiles) {
-        F.split_tiles = std::max(1, F.num_tiles / kSplitDiv);
-        // sixteenth-waves (4 lanes) must hold whole pixels too
-        if (kSplit16Div > 0 && 4 % F.spp == 0) {
-            // a lone shard's (one-sample waves, below) more (kSplit16DivSample)
-            const bool sample_waves = F.spp == 4 && !overlapped_frame(ctx, prm) && group_sample_waves(ctx) && !batch;
-            const int div = sample_waves ? kSplit16DivSample : kSplit16Div;
-            F.split16_tiles = std::min(F.split_tiles, std::max(1, F.num_tiles / div));
-            F.split_tiles -= F.split16_tiles;
-        }
-    } else if (F.tile_order && !count && !levels && kSplit16DivLarge > 0 && 4 % F.spp == 0 &&
-               (F.num_tiles <= kSplit16MaxTiles || (kSplitSync && !overlapped_frame(ctx, prm)))) {
-        const bool lone_shard = F.num_tiles <= kSplit16MaxTiles && !overlapped_frame(ctx, prm);
-        // (one-sample waves below: kSplit16DivLoneSample)
-        const bool sample_waves =
-            lone_shard && F.spp == 4 && F.num_tiles <= kSample16LoneTiles && group_sample_waves(ctx) && !batch;
-        const int div = sample_waves ? kSplit16DivLoneSample
-                        : lone_shard ? kSplit16DivLone
-                        : F.num_tiles > kSplit16MaxTiles ? kSplit16DivWhole : kSplit16DivLarge;
-        F.split16_tiles = std::max(1, F.num_tiles / div);
-    }
+    F.tile_order = P.use_order ? (const int *)ls->order.p : nullptr;
+    F.tile_cost = P.measure ? (unsigned *)ls->cost.p : nullptr;
     // the split-tile instance's shadow occluder hints (packet.h packet_trace
     // HINT): leaf refs of the tree they were recorded on, so cleared whenever
     // the scene changed (another tree's refs may lie outside this one's arrays)
-    if (!count && !levels && (F.split_tiles > 0 || F.split16_tiles > 0)) {
+    if (P.hints) {
         const size_t hb = (size_t)F.num_tiles * rtd::kHintLights * sizeof(int);
         bool clear = ls->hints_scene != ctx->scene_version || ls->hints_key != key;
         if (hb > ls->hints.cap) {
@@ -556,19 +440,8 @@ int lpt_prepare(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, bool
         ls->hints_key = key;
         F.shadow_hint = (int *)ls->hints.p;
     }
-    // In small shards the finely split tiles go one step further, to a sample
-    // per wave (F.s16_shift 0; the shard instance sums each pixel's four
-    // samples when the last arrives): a pixel's four samples no longer wait for
-    // each other's divergent mirror chains.  Lone frames only (nothing beside
-    // them hides their slowest chain): a 1/8 C3 shard's single frame -20 %, a
-    // 1/4 shard's -15 %; a lone 1/2 shard +5 %, whole frames +6 %; with four
-    // frames in flight a 1/8 shard's throughput is -3 % to +-0 (r04r, r04ag,
-    // r04ai, 200-frame runs alternated on one box).  The bands of a multi-device
-    // frame too, unless rt_debug_set(RT_DEBUG_GROUP_SAMPLE_WAVES, 0)
-    // (group_sample_waves above).
-    if (F.split16_tiles > 0 && !count && !levels && F.spp == 4 && F.num_tiles <= rtk::kShardTilesMax &&
-        F.num_tiles <= kSample16LoneTiles && !overlapped_frame(ctx, prm) && group_sample_waves(ctx) && !batch) {
-        F.s16_shift = 0;
+    // one-sample waves: a finely split tile's 64 samples and its pixels' arrival counts
+    if (P.handoff) {
         const size_t sb = (size_t)F.split16_tiles * rtd::kWaveSize * 4 * sizeof(float);
         const size_t cb = (size_t)F.split16_tiles * (rtd::kWaveSize / 4) * sizeof(int);
         HIP_OR_FAIL(ctx, ensure(ctx, ls->split_samples, sb));
@@ -579,47 +452,18 @@ int lpt_prepare(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, bool
         F.split_samples = (float *)ls->split_samples.p;
         F.split_count = (int *)ls->split_count.p;
     }
-    // The sorted order ends with the tiles the last measurement found to be
-    // sky (cost key 0, row order): with other frames in flight beside this
-    // one, sky_batch_kernel takes them rtk::kSkyBatch a wave after
-    // render_kernel, together with the launch's tallies (C3 frames in flight
-    // -4.9 % per frame, r06d; a lone frame, whose critical path the batches
-    // lengthen, +0.5 % C3, +5 % a 1/8 shard: abx_r05t).  Only the grids depend on this count (a stale one costs time,
-    // not pixels: a batch renders any tile that is not sky in full).
-    if (F.tile_order && !count && !levels && rtk::kSkyBatch > 1 && F.num_tiles > kSkyMinTiles &&
-        (overlapped_frame(ctx, prm) || (kSkyLone && F.num_tiles > rtk::kShardTilesMax)))
-        // (render_kernel keeps one wave at least: its launch and tallies stay, an all-sky view included)
-        F.sky_batch_tiles = std::max(0, std::min(ls->sky_tail, F.num_tiles - F.split_tiles - F.split16_tiles - 1));
     {
         char b[160];
         snprintf(b, sizeof b, " lpt: frame=%lld sky_tail=%d known=%d pending=%d overlapped=%d sky_waits=%lld",
-                 ls->frames, ls->sky_tail, (int)ls->sky_known, (int)ls->sky_pending, (int)overlapped_frame(ctx, prm),
+                 ls->frames, ls->sky_tail, (int)ls->sky_known, (int)ls->sky_pending, (int)in.overlapped,
                  ctx->sky_waits);
         ctx->last_lpt = b;
-    }
-    if (levels && !(F.max_bounces > rtd::kMaxBounces)) {
-        // the levels kernel dispatches XCD-aware stripes (trace_levels.hip)
-        // in row order, without splits.  Its 16-spp instance (the one with
-        // the sky test) measures which tiles are sky, and whole frames in
-        // flight leave those to sky_batch_kernel: its positions are then the
-        // measured non-sky tiles, longest first (trace_levels.hip kLvRowKeys:
-        // or in row order) (C4 all-sky frames cost 0.955 ms in flight as a
-        // wave per tile; skycost, r05z).
-        if (F.spp == 16 && rtk::kSkyBatch > 1) {
-            if (F.tile_order && !count && overlapped_frame(ctx, prm))
-                F.sky_batch_tiles = std::max(0, std::min(ls->sky_tail, F.num_tiles - 1));
-            if (F.sky_batch_tiles == 0) F.tile_order = nullptr;  // plain stripes
-        } else {
-            F.tile_order = nullptr;
-            F.tile_cost = nullptr;
-            lpt_sort = false;
-        }
     }
     // render_kernel's ray tallies: one plain store per wave into this slot's
     // buffer, reduced after the launch on the same stream (an atomic per wave
     // holds the wave's slot for its round trip: C2 -13 %, C3 -4 %)
-    if (!count) {  // render_kernel and render_levels_kernel
-        const size_t bytes = (size_t)rtk::render_mega_waves(F) * sizeof(uint4);
+    if (P.tallies) {  // render_kernel and render_levels_kernel
+        const size_t bytes = (size_t)P.waves * sizeof(uint4);
         if (bytes > ls->wave_counts.cap) {  // a new buffer carries no launch's tag
             HIP_OR_FAIL(ctx, ensure(ctx, ls->wave_counts, bytes));
             HIP_OR_FAIL(ctx, hipMemsetAsync(ls->wave_counts.p, 0, ls->wave_counts.cap, ctx->stream));
@@ -628,9 +472,10 @@ int lpt_prepare(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, bool
         if (++ctx->count_tag == 0) ++ctx->count_tag;
         F.count_tag = ctx->count_tag;
     }
+    const bool levels = P.instance == rtp::kLevels || P.instance == rtp::kDeep;  // (or deep)
 #ifdef RT_EXP_PERSIST
     // measuring builds: whole frames' non-split launches as resident waves
-    if (!count && !levels && F.split_tiles == 0 && F.split16_tiles == 0 && F.num_tiles > kSplit16MaxTiles) {
+    if (!levels && F.split_tiles == 0 && F.split16_tiles == 0 && F.num_tiles > rtp::kSplit16MaxTiles) {
         HIP_OR_FAIL(ctx, ensure(ctx, ls->persist_ctr, 8 * 16 * sizeof(int)));
         HIP_OR_FAIL(ctx, hipMemsetAsync(ls->persist_ctr.p, 0, 8 * 16 * sizeof(int), ctx->stream));
         F.persist_ctr = (int *)ls->persist_ctr.p;
@@ -640,8 +485,8 @@ int lpt_prepare(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, bool
     }
 #endif
     // measuring builds (rt_debug_set RT_DEBUG_WAVE_CLOCKS): the launch's per-wave clocks
-    if (rtk::kWaveClockBuild && ctx->debug_wave_clock && !count && !levels) {
-        const size_t bytes = (size_t)rtk::render_mega_waves(F) * sizeof(uint4);
+    if (rtk::kWaveClockBuild && ctx->debug_wave_clock && !levels) {
+        const size_t bytes = (size_t)P.waves * sizeof(uint4);
         HIP_OR_FAIL(ctx, ensure(ctx, ctx->wave_clock, bytes));
         HIP_OR_FAIL(ctx, hipMemsetAsync(ctx->wave_clock.p, 0, bytes, ctx->stream));
         F.wave_clock = (uint4 *)ctx->wave_clock.p;
@@ -650,18 +495,7 @@ int lpt_prepare(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, bool
     return RT_OK;
 }
 
-// Whether a frame like F (same layout, same overlap) takes sky batches, i.e.
-// whether the sky tail of F's order is worth a host wait (lpt_prepare's rules:
-// megakernel frames in flight of more than kSkyMinTiles tiles, 16-spp levels
-// frames in flight).  Lone frames, small shares and rt_render's row slabs
-// never use the tail, so their first sort does not wait for its count.
-static bool sky_tail_usable(const rt_ctx *ctx, const rtd::FrameDev &F) {
-    if (rtk::kSkyBatch <= 1 || F.max_bounces > rtd::kMaxBounces) return false;
-    if (ctx->S.bvh4 && F.spp >= 16) return F.spp == 16 && F.in_flight;
-    return F.num_tiles > kSkyMinTiles && (F.in_flight || (kSkyLone && F.num_tiles > rtk::kShardTilesMax));
-}
-
-int lpt_sort_now(rt_ctx *ctx, const rtd::FrameDev &F, LptSlot *ls) {
+int lpt_sort_now(rt_ctx *ctx, const rtd::FrameDev &F, LptSlot *ls, const rtp::Plan &P) {
     HIP_OR_FAIL(ctx, rtk::sort_tiles_by_cost((const unsigned *)ls->cost.p, (unsigned *)ls->cost_sorted.p,
                                              (const int *)ls->iota.p, (int *)ls->order.p, F.num_tiles,
                                              ls->scratch.p, ls->scratch.cap, ctx->stream));
@@ -674,7 +508,7 @@ int lpt_sort_now(rt_ctx *ctx, const rtd::FrameDev &F, LptSlot *ls) {
         HIP_OR_FAIL(ctx, rtk::launch_sky_count((const unsigned *)ls->cost_sorted.p, F.num_tiles, ++ls->sky_seq, dev,
                                                ctx->stream));
         ls->sky_pending = true;
-        if (!ls->sky_known && sky_tail_usable(ctx, F)) {
+        if (!ls->sky_known && P.sky_tail_usable) {
             // the slot's first order that a frame in flight can use: wait for
             // its count once (frames in flight run far ahead of the device, so
             // a lagged count of the first sort would arrive only after the
@@ -743,15 +577,15 @@ static void fill_batch(const rtd::FrameDev &H, const BatchIn &bi, rtd::FrameBatc
     }
 }
 
-// Enqueues the trace launch(es) of F on the context's stream (bi: F is the
-// head of a batch launch).
-int launch_frame(rt_ctx *ctx, rtd::FrameDev &F, const Path &P, const rtw::Args &A, int chunk_tiles,
-                 const BatchIn *bi) {
+// Enqueues the trace launch(es) of F on the context's stream as lpt_prepare
+// planned them (bi: F is the head of a batch launch).
+int launch_frame(rt_ctx *ctx, rtd::FrameDev &F, const Path &P, const rtp::Plan &plan, const rtw::Args &A,
+                 int chunk_tiles, const BatchIn *bi) {
     if (bi) {
         static thread_local rtd::FrameBatch B;  // (3.3 KB: off the stack)
         fill_batch(F, *bi, B);
         const char *inst = nullptr;
-        HIP_OR_FAIL(ctx, rtk::launch_render_batch(ctx->S, B, ctx->stream, &inst));
+        HIP_OR_FAIL(ctx, rtk::launch_render_batch(ctx->S, B, plan, ctx->stream, &inst));
         if (inst) {
             char b[256];
             snprintf(b, sizeof b, "%s frames=%d tiles=%d split16=%d split=%d s16_shift=%d rows=%d band=%d/%d sky=%d",
@@ -766,7 +600,7 @@ int launch_frame(rt_ctx *ctx, rtd::FrameDev &F, const Path &P, const rtw::Args &
         HIP_OR_FAIL(ctx, rtk::launch_render_packet(ctx->S, F, P.count, ctx->stream));
     else if (P.mega) {
         const char *inst = nullptr;
-        HIP_OR_FAIL(ctx, rtk::launch_render_mega(ctx->S, F, P.count, ctx->stream, &inst));
+        HIP_OR_FAIL(ctx, rtk::launch_render_mega(ctx->S, F, plan, ctx->stream, &inst));
         if (inst) {  // rt_debug_read RT_DEBUG_LAST_LAUNCH
             char b[256];
             snprintf(b, sizeof b, "%s tiles=%d split16=%d split=%d s16_shift=%d rows=%d band=%d/%d sky=%d", inst,
@@ -823,7 +657,7 @@ int run_frame(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, void *
     struct Launch {
         rtd::FrameDev F;
         LptSlot *ls;
-        bool sort;
+        rtp::Plan plan;  // its dispatch (lpt_prepare)
         hipStream_t stream;
         int r0, r1;
     };
@@ -878,7 +712,7 @@ int run_frame(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, void *
             L.F.local_rows = L.r1 - L.r0;
             L.F.num_tiles = L.F.res_x > 0 ? L.F.tiles_x * ((L.F.local_rows + L.F.tile_h - 1) / L.F.tile_h) : 0;
             L.F.out = (char *)d_out + (size_t)L.r0 * row_bytes;
-            int st = lpt_prepare(ctx, L.F, prm, P.mega, P.count, k, L.ls, L.sort);
+            int st = lpt_prepare(ctx, L.F, prm, P.mega, P.count, k, L.ls, L.plan);
             if (st) return st;
             launches.push_back(L);
         }
@@ -890,7 +724,7 @@ int run_frame(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, void *
         L.F = F;
         L.stream = base;
         // (a batch keeps its order apart from single frames on the same stream: slot kBatchSlab + frames)
-        int st = lpt_prepare(ctx, L.F, prm, P.mega, P.count, bi ? kBatchSlab + bi->n : 0, L.ls, L.sort);
+        int st = lpt_prepare(ctx, L.F, prm, P.mega, P.count, bi ? kBatchSlab + bi->n : 0, L.ls, L.plan);
         if (st) return st;
         launches.push_back(L);
     }
@@ -924,7 +758,7 @@ int run_frame(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, void *
             ctx->stream = launches[k].stream;
             if (k == ctx->debug_fail_slab)  // rt_debug_set(RT_DEBUG_FAIL_SLAB): tests only
                 return fail(ctx, RT_E_INTERNAL, "injected failure before slab %d (RT_DEBUG_FAIL_SLAB)", k);
-            int st = launch_frame(ctx, launches[k].F, P, A, chunk_tiles, nullptr);
+            int st = launch_frame(ctx, launches[k].F, P, launches[k].plan, A, chunk_tiles, nullptr);
             if (st) return st;
             HIP_OR_FAIL(ctx, hipEventRecord(ctx->slab_done[k], ctx->stream));
             // the copier thread copies slab k once its launch has ended, while
@@ -940,9 +774,9 @@ int run_frame(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, void *
         if (nslab > 1) HIP_OR_FAIL(ctx, hipStreamWaitEvent(base, ctx->slab_done[nslab - (nslab & 1 ? 2 : 1)], 0));
         HIP_OR_FAIL(ctx, hipEventRecord(ctx->ev1, base));
         for (Launch &L : launches) {  // after the timed region: the order of the next frames
-            if (!L.sort) continue;
+            if (!L.plan.measure) continue;
             ctx->stream = L.stream;
-            int st = lpt_sort_now(ctx, L.F, L.ls);
+            int st = lpt_sort_now(ctx, L.F, L.ls, L.plan);
             if (st) return st;
         }
         ctx->stream = base;
@@ -952,11 +786,11 @@ int run_frame(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, void *
         HIP_OR_FAIL(ctx, ctx->copier.wait());  // every slab is in the caller's buffer
     } else {
         Launch &L = launches[0];
-        int st = launch_frame(ctx, L.F, P, A, chunk_tiles, bi);
+        int st = launch_frame(ctx, L.F, P, L.plan, A, chunk_tiles, bi);
         if (st) return st;
         if (async) {
-            if (L.sort) {
-                st = lpt_sort_now(ctx, L.F, L.ls);
+            if (L.plan.measure) {
+                st = lpt_sort_now(ctx, L.F, L.ls, L.plan);
                 if (st) return st;
             }
             st = record_async_end(ctx);
@@ -980,13 +814,13 @@ int run_frame(rt_ctx *ctx, rtd::FrameDev &F, const rt_render_params *prm, void *
             // the stream follows it)
             HIP_WAIT(ctx, hipMemcpyAsync(host_out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
             HIP_WAIT(ctx, hipStreamSynchronize(ctx->stream));  // (a page-locked host_out: the copy was async)
-            if (L.sort) {
-                st = lpt_sort_now(ctx, L.F, L.ls);
+            if (L.plan.measure) {
+                st = lpt_sort_now(ctx, L.F, L.ls, L.plan);
                 if (st) return st;
             }
             sync_done = true;
-        } else if (L.sort) {  // after the timed region: the order of the next frames
-            st = lpt_sort_now(ctx, L.F, L.ls);
+        } else if (L.plan.measure) {  // after the timed region: the order of the next frames
+            st = lpt_sort_now(ctx, L.F, L.ls, L.plan);
             if (st) return st;
         }
     }

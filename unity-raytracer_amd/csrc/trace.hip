@@ -319,7 +319,7 @@ __device__ __forceinline__ f3 shade_path(const SceneDev &S, const FrameDev &F, f
 // kStackSize) six waves fit a CU's LDS too; at 24 entries the LDS capped the
 // CU at 23 one-wave workgroups, so earlier "6 waves" builds only spilled more.
 // C3 -7 % single frame / -5 % frames in flight, C2 -5 % / -2 % (r04h).  Small
-// frames (row shards of <= kShardTiles tiles, whose time is their slowest
+// frames (row shards of <= rtp::kShardTilesMax tiles, whose time is their slowest
 // waves): 5 (96 VGPRs, fewer spills) — 6 made a 1/8 shard 3-9 % slower.
 #ifdef RT_EXP_MKWAVES
 constexpr int kMkMinWaves = RT_EXP_MKWAVES;  // measuring builds only
@@ -339,16 +339,6 @@ constexpr int kStackShard = 24;
 // (shift 0, rt_frame.cpp lpt_prepare): a pixel's four samples then meet in
 // F.split_samples and the last to arrive sums them (render_tile).
 __device__ __forceinline__ int s16_shift(const FrameDev &F) { return __builtin_amdgcn_readfirstlane(F.s16_shift); }
-constexpr int kShardTiles = rtk::kShardTilesMax;  // a 1/2 shard of 1080p at 4 spp
-// ... but a shard of more tiles than this with other frames in flight beside
-// it takes the 6-wave split instance: a 1/4 C3 share in flight -11.4 % per
-// frame (0.0812 -> 0.0719 ms), a 1/8 share +8 %, lone shards +7 to +21 % (r06j);
-// then (r06k) 1/2 -13.6 %, 1/4 -9.8 %, 1/8 +-0
-#ifdef RT_EXP_SHARDW6
-constexpr int kShardW6InFlight = RT_EXP_SHARDW6;  // measuring builds only
-#else
-constexpr int kShardW6InFlight = 24000;
-#endif
 // Waves per megakernel workgroup.  A workgroup's slot is recycled only when
 // all of its waves are done, and path lengths vary a lot between tiles, so
 // small workgroups keep the CUs fuller near the end of each wave "round".
@@ -1293,115 +1283,76 @@ hipError_t launch_refresh_cut(const BvhNode4 *nodes, CutTable *out, hipStream_t 
     return hipGetLastError();
 }
 
-// all-packet levels pay off where a wave's tile is small on screen (its
-// mirror rays stay coherent): 16+ samples per pixel = at most 2x2 pixels
-constexpr int kLevelsMinSpp = 16;
-
-
 // one-wave tally blocks of sky_batch_kernel for `waves` entries (as many
 // threads as wave_counts_kernel's up to 64 x 256)
 static int tail_count_blocks(int waves) { return std::max(1, std::min(256, (waves + 255) / 256)); }
 
-hipError_t launch_render_mega(const SceneDev &S, const FrameDev &F0, bool count_tests, hipStream_t stream,
+// The kernels of rtp::Instance, from the list that names them (dispatch_plan.h).
+static_assert(kMkMinWaves == RT_PLAN_W6 && kMkMinWavesShard == RT_PLAN_W5, "the instance names show the launch bounds");
+#define RT_PLAN_X(id, kernel, ...) (const void *)&kernel<__VA_ARGS__>,
+static const void *const kInstanceKernels[rtp::kInstances] = {RT_PLAN_INSTANCES(RT_PLAN_X)};
+#undef RT_PLAN_X
+
+// After a render launch of H (a frame, or the head of batch B): the order's
+// sky tail and the launch's per-wave tallies -> counters in one launch, or the
+// tallies alone.
+static hipError_t launch_tail(const SceneDev &S, const FrameDev &H, const FrameBatch *B, const rtp::Plan &P,
+                              hipStream_t stream) {
+    if (P.sky_batch_tiles > 0) {
+        const int sb = (P.sky_batch_tiles + rtk::kSkyBatch - 1) / rtk::kSkyBatch;
+        const dim3 g(sb + tail_count_blocks(P.waves));
+        if (B) {
+            hipLaunchKernelGGL(sky_batch_batch_kernel, g, dim3(kMkThreads), 0, stream, SkyArgs<true>{S, *B, sb, P.waves});
+        } else {
+            if (P.tail != rtp::kSkyTail && P.tail != rtp::kSkyTailQ4) return hipErrorInvalidValue;
+            SkyArgs<false> A{S, H, sb, P.waves};
+            void *args[] = {(void *)&A};
+            return hipLaunchKernel(kInstanceKernels[P.tail], g, dim3(kMkThreads), args, 0, stream);
+        }
+    } else if (P.tallies) {  // (the entries lpt_prepare sized the buffer for)
+        hipLaunchKernelGGL(wave_counts_kernel, dim3(std::max(1, std::min(64, (P.waves + 1023) / 1024))), dim3(256), 0, stream,
+                           (const uint4 *)H.wave_counts, P.waves, H.count_tag, H.primary_total, H.counters);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_render_mega(const SceneDev &S, const FrameDev &F0, const rtp::Plan &P, hipStream_t stream,
                               const char **instance) {
     const char *dummy = nullptr;
     const char *&name = instance ? *instance : dummy;
     name = nullptr;
     if (F0.num_tiles <= 0) return hipSuccess;
+    if (P.instance > rtp::kLevels) return hipErrorInvalidValue;
     FrameDev F = F0;
     F.primary_total = active_samples(F.res_x, F.res_y, F.local_rows, F.row0, F.band_index, F.band_count, F.band_rows,
                                      F.spp);
-    int blocks = (render_mega_waves(F) + kMkWaves - 1) / kMkWaves;
+    if (P.instance == rtp::kLevels) {
+        const hipError_t e = launch_render_levels(S, F, stream, &name);
+        return e != hipSuccess ? e : launch_tail(S, F, nullptr, P, stream);  // (one wave per position, no splits)
+    }
+    int blocks = (P.waves + kMkWaves - 1) / kMkWaves;
 #ifdef RT_EXP_PERSIST
-    if (F.persist_waves > 0 && !count_tests && F.split_tiles == 0 && F.split16_tiles == 0 && F.max_bounces <= kMaxBounces &&
-        !(S.bvh4 && F.spp >= kLevelsMinSpp))
+    if (F.persist_waves > 0 && (P.instance == rtp::kQ4 || P.instance == rtp::kPlain))
         blocks = std::min(blocks, F.persist_waves);
     else
         F.persist_waves = 0;
 #endif
-    const bool q4 = F.spp == 4 && F.tile_w == 4 && F.tile_h == 4;
-    // a small frame: its slowest waves set its time (unless frames in flight hide them)
-    const bool shard = F.num_tiles <= kShardTiles && !(F.in_flight && F.num_tiles > kShardW6InFlight);
-    const bool split = F.split_tiles > 0 || F.split16_tiles > 0;
-    constexpr int W5 = kMkMinWavesShard;
-#if !defined(RT_EXP_MKWAVES) && !defined(RT_EXP_MKWSHARD)
-    static_assert(kMkMinWaves == 6 && W5 == 5, "instance names below");
-#endif
-#define RT_LAUNCH(K, NAME)                                                                  \
-    do {                                                                                    \
-        if (blocks > 0) hipLaunchKernelGGL(K, dim3(blocks), dim3(kMkThreads), 0, stream, S, F); \
-        name = NAME;                                                                        \
-    } while (0)
-    if (F.max_bounces > kMaxBounces) {  // mirror chains may outgrow the fold stack
-        if (count_tests)
-            RT_LAUNCH((render_kernel<true, false, true, false, W5>), "render_kernel<true, false, true, false, 5, false>");
-        else
-            RT_LAUNCH((render_kernel<false, false, true, false, W5>), "render_kernel<false, false, true, false, 5, false>");
-    } else if (count_tests)
-        RT_LAUNCH((render_kernel<true, false, false, false, W5>), "render_kernel<true, false, false, false, 5, false>");
-    else if (split && q4 && shard && F.s16_shift == 0)
-        RT_LAUNCH((render_kernel<false, true, false, true, W5, true>), "render_kernel<false, true, false, true, 5, true>");
-    else if (split && q4 && shard)
-        RT_LAUNCH((render_kernel<false, true, false, true, W5>), "render_kernel<false, true, false, true, 5, false>");
-    else if (split && q4)
-        RT_LAUNCH((render_kernel<false, true, false, true>), "render_kernel<false, true, false, true, 6, false>");
-    else if (split && shard && F.s16_shift == 0)
-        RT_LAUNCH((render_kernel<false, true, false, false, W5, true>),
-                  "render_kernel<false, true, false, false, 5, true>");
-    else if (split && shard)
-        RT_LAUNCH((render_kernel<false, true, false, false, W5>), "render_kernel<false, true, false, false, 5, false>");
-    else if (split)
-        RT_LAUNCH((render_kernel<false, true>), "render_kernel<false, true, false, false, 6, false>");
-    else if (S.bvh4 && F.spp >= kLevelsMinSpp) {
-        const hipError_t e = launch_render_levels(S, F, stream);
-        static const char *const lv[2][3] = {{"render_levels_kernel<6, 8, 4>", "render_levels_kernel<6, 16, 4>",
-                                              "render_levels_kernel<6, 32, 4>"},
-                                             {"render_levels_kernel<7, 8, 8>", "render_levels_kernel<7, 16, 8>",
-                                              "render_levels_kernel<7, 32, 8>"}};
-        name = F.spp > 16 && F.spp != 64 ? "render_levels_kernel<7, 32, 0>"
-                                         : lv[F.spp <= 16 ? 0 : 1][F.max_bounces <= 8 ? 0 : F.max_bounces <= 16 ? 1 : 2];
+    if (blocks > 0) {
+        void *args[] = {(void *)&S, (void *)&F};
+        const hipError_t e = hipLaunchKernel(kInstanceKernels[P.instance], dim3(blocks), dim3(kMkThreads), args, 0, stream);
         if (e != hipSuccess) return e;
-        const int waves = F.num_tiles - F.sky_batch_tiles;  // one wave per position, no splits
-        if (F.sky_batch_tiles > 0 && F.tile_order && F.wave_counts) {  // (16 spp in flight: the order's sky tail)
-            const int sb = (F.sky_batch_tiles + rtk::kSkyBatch - 1) / rtk::kSkyBatch;
-            hipLaunchKernelGGL(sky_batch_kernel<false>, dim3(sb + tail_count_blocks(waves)), dim3(kMkThreads), 0, stream,
-                               SkyArgs<false>{S, F, sb, waves});
-            return hipGetLastError();
-        }
-        if (!F.wave_counts) return hipGetLastError();
-        hipLaunchKernelGGL(wave_counts_kernel, dim3(std::max(1, std::min(64, (waves + 1023) / 1024))), dim3(256), 0, stream,
-                           (const uint4 *)F.wave_counts, waves, F.count_tag, F.primary_total, F.counters);
-        return hipGetLastError();
     }
-    else if (q4)
-        RT_LAUNCH((render_kernel<false, false, false, true>), "render_kernel<false, false, false, true, 6, false>");
-    else
-        RT_LAUNCH(render_kernel<false>, "render_kernel<false, false, false, false, 6, false>");
-#undef RT_LAUNCH
-    if (!count_tests && F.sky_batch_tiles > 0 && F.tile_order && F.max_bounces <= kMaxBounces && F.wave_counts) {
-        // the order's sky tail and the launch's tallies in one launch
-        const int sb = (F.sky_batch_tiles + rtk::kSkyBatch - 1) / rtk::kSkyBatch;
-        const int waves = render_mega_waves(F);
-        const dim3 g(sb + tail_count_blocks(waves));
-        if (q4)
-            hipLaunchKernelGGL(sky_batch_kernel<true>, g, dim3(kMkThreads), 0, stream, SkyArgs<false>{S, F, sb, waves});
-        else
-            hipLaunchKernelGGL(sky_batch_kernel<false>, g, dim3(kMkThreads), 0, stream, SkyArgs<false>{S, F, sb, waves});
-        return hipGetLastError();
-    }
-    if (!count_tests && F.wave_counts) {  // the launch's per-wave tallies -> counters
-        const int waves = render_mega_waves(F);  // the entries lpt_prepare sized the buffer for
-        hipLaunchKernelGGL(wave_counts_kernel, dim3(std::max(1, std::min(64, (waves + 1023) / 1024))), dim3(256), 0, stream,
-                           (const uint4 *)F.wave_counts, waves, F.count_tag, F.primary_total, F.counters);
-    }
-    return hipGetLastError();
+    name = rtp::instance_name(P.instance);
+    return launch_tail(S, F, nullptr, P, stream);
 }
 
-hipError_t launch_render_batch(const SceneDev &S, const FrameBatch &B0, hipStream_t stream, const char **instance) {
+hipError_t launch_render_batch(const SceneDev &S, const FrameBatch &B0, const rtp::Plan &P, hipStream_t stream,
+                               const char **instance) {
     const char *dummy = nullptr;
     const char *&name = instance ? *instance : dummy;
     name = nullptr;
     if (B0.frames < 1 || B0.frames > kMaxBatch || B0.f[0].num_tiles <= 0) return hipErrorInvalidValue;
+    if (P.instance != rtp::kBatch && P.instance != rtp::kBatchSplit) return hipErrorInvalidValue;
     static thread_local FrameBatch B;
     B = B0;
     FrameDev &H = B.f[0];
@@ -1409,31 +1360,11 @@ hipError_t launch_render_batch(const SceneDev &S, const FrameBatch &B0, hipStrea
     H.primary_total = active_samples(H.res_x, H.res_y, H.local_rows, H.row0, H.band_index, H.band_count,
                                      H.band_rows, H.spp) *
                       (unsigned long long)B.frames;
-    const int blocks = render_mega_waves(H);
-    if (H.split_tiles > 0 || H.split16_tiles > 0) {
-        hipLaunchKernelGGL(render_batch_kernel<true>, dim3(blocks), dim3(kMkThreads), 0, stream, S, B);
-        name = "render_batch_kernel<true>";
-    } else {
-        hipLaunchKernelGGL(render_batch_kernel<false>, dim3(blocks), dim3(kMkThreads), 0, stream, S, B);
-        name = "render_batch_kernel<false>";
-    }
-    if (H.sky_batch_tiles > 0 && H.tile_order && H.wave_counts) {
-        // the batch order's sky tail and the launch's tallies in one launch
-        const int sb = (H.sky_batch_tiles + rtk::kSkyBatch - 1) / rtk::kSkyBatch;
-        hipLaunchKernelGGL(sky_batch_batch_kernel, dim3(sb + tail_count_blocks(blocks)), dim3(kMkThreads), 0, stream,
-                           SkyArgs<true>{S, B, sb, blocks});
-    } else if (H.wave_counts) {
-        hipLaunchKernelGGL(wave_counts_kernel, dim3(std::max(1, std::min(64, (blocks + 1023) / 1024))), dim3(256), 0,
-                           stream, (const uint4 *)H.wave_counts, blocks, H.count_tag, H.primary_total, H.counters);
-    }
-    return hipGetLastError();
-}
-
-int render_mega_waves(const FrameDev &F) {
-    // (the last F.sky_batch_tiles positions are sky_batch_kernel's; the counting launch's F has none)
-    return F.num_tiles <= 0 ? 0
-                            : F.num_tiles - F.sky_batch_tiles + ((64 >> F.s16_shift) - 1) * F.split16_tiles +
-                                  3 * F.split_tiles;
+    void *args[] = {(void *)&S, (void *)&B};
+    const hipError_t e = hipLaunchKernel(kInstanceKernels[P.instance], dim3(P.waves), dim3(kMkThreads), args, 0, stream);
+    if (e != hipSuccess) return e;
+    name = rtp::instance_name(P.instance);
+    return launch_tail(S, H, &B, P, stream);
 }
 
 __global__ __launch_bounds__(256) void sky_count_kernel(const unsigned *sorted, int n, unsigned seq,

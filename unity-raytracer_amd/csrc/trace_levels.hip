@@ -343,7 +343,10 @@ __global__ __launch_bounds__(kWaveSize, MIN_WAVES) void render_levels_kernel(Sce
 
 namespace rtk {
 
-hipError_t launch_render_levels(const SceneDev &S, const FrameDev &F0, hipStream_t stream) {
+hipError_t launch_render_levels(const SceneDev &S, const FrameDev &F0, hipStream_t stream, const char **instance) {
+    const char *dummy = nullptr;
+    const char *&name = instance ? *instance : dummy;
+    name = nullptr;
     if (F0.num_tiles <= 0) return hipSuccess;
     FrameDev F = F0;
     // whole groups of eight stripes (render_levels_kernel's XCD-aware dispatch)
@@ -357,23 +360,32 @@ hipError_t launch_render_levels(const SceneDev &S, const FrameDev &F0, hipStream
     // the fold stack's depth bucket (render_levels_kernel FD); frames deeper
     // than kMaxBounces never come here (rt_frame.cpp frame_path)
     const int fd = F.max_bounces <= 8 ? 8 : F.max_bounces <= 16 ? 16 : kMaxBounces;
+#if !defined(RT_EXP_LVLOW) && !defined(RT_EXP_LVHIGH)
+    static_assert(kLvWavesLowSpp == 6 && kLvWavesHighSpp == 7 && kMaxBounces == 32, "instance names below");
+#endif
+#define RT_LAUNCH(W, FD, FIX, ARGS)                                                             \
+    do {                                                                                        \
+        hipLaunchKernelGGL((render_levels_kernel<W, FD, FIX>), g, b, 0, stream, S, F);          \
+        name = "render_levels_kernel<" ARGS ">";                                                \
+    } while (0)
     if (F.spp <= 16) {  // 16 spp: FIX 4
         if (fd == 8)
-            hipLaunchKernelGGL((render_levels_kernel<kLvWavesLowSpp, 8, 4>), g, b, 0, stream, S, F);
+            RT_LAUNCH(kLvWavesLowSpp, 8, 4, "6, 8, 4");
         else if (fd == 16)
-            hipLaunchKernelGGL((render_levels_kernel<kLvWavesLowSpp, 16, 4>), g, b, 0, stream, S, F);
+            RT_LAUNCH(kLvWavesLowSpp, 16, 4, "6, 16, 4");
         else
-            hipLaunchKernelGGL((render_levels_kernel<kLvWavesLowSpp, kMaxBounces, 4>), g, b, 0, stream, S, F);
+            RT_LAUNCH(kLvWavesLowSpp, kMaxBounces, 4, "6, 32, 4");
     } else if (F.spp == 64) {
         if (fd == 8)
-            hipLaunchKernelGGL((render_levels_kernel<kLvWavesHighSpp, 8, 8>), g, b, 0, stream, S, F);
+            RT_LAUNCH(kLvWavesHighSpp, 8, 8, "7, 8, 8");
         else if (fd == 16)
-            hipLaunchKernelGGL((render_levels_kernel<kLvWavesHighSpp, 16, 8>), g, b, 0, stream, S, F);
+            RT_LAUNCH(kLvWavesHighSpp, 16, 8, "7, 16, 8");
         else
-            hipLaunchKernelGGL((render_levels_kernel<kLvWavesHighSpp, kMaxBounces, 8>), g, b, 0, stream, S, F);
+            RT_LAUNCH(kLvWavesHighSpp, kMaxBounces, 8, "7, 32, 8");
     } else {  // 25 / 36 / 49 spp
-        hipLaunchKernelGGL((render_levels_kernel<kLvWavesHighSpp, kMaxBounces, 0>), g, b, 0, stream, S, F);
+        RT_LAUNCH(kLvWavesHighSpp, kMaxBounces, 0, "7, 32, 0");
     }
+#undef RT_LAUNCH
     return hipGetLastError();
 }
 
